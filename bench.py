@@ -24,6 +24,11 @@ the reference's index order (ESC_RENDER_INDEX_ORDER) -- BASELINE's "brute-force 
 `cpu_baseline` times the test oracle (oracle/rt_oracle.c, a strict-IEEE restatement of the
 reference's scalar path: the reference's ISPC path cannot be built, `ispc` is not in the image)
 on a bounded sample of rows of the SAME frame on all host cores, rank 0 at N=1 only.
+
+A plain run sets up, warms up, counts the rays of one frame, times the K steps and prints the
+line (`value`, `ms_per_step`, `roofline`, `valu`).  `--full` adds the runs of their own:
+`kernel_split`, `linear`, `frame_latency_ms`, `host`, `cpu_baseline` / `gpu_vs_cpu` and `accel`.
+`--dump-outputs DIR` writes the frame of the last timed step (see its help).
 """
 import argparse
 import json
@@ -114,7 +119,8 @@ def parse():
                          "ESC_RENDER_INDEX_ORDER, every pair in the reference's index order, is the "
                          "TIMED path (what tools/profile.sh wraps for the `linear` counters)")
     ap.add_argument("--linear-steps", type=int, default=-1,
-                    help="frames of the `linear` leg (default: min(steps, 5); 0 = skip)")
+                    help="frames of the `linear` leg (default: min(steps, 5) with --full, else 0; "
+                         "0 = skip)")
     ap.add_argument("--graph", action="store_true",
                     help="timed steps replay a recorded frame (esc_frame_record: one hipGraphLaunch "
                          "per frame) instead of calling esc_render_strips (parameter block + kernel "
@@ -142,14 +148,25 @@ def parse():
                     help="what rank 0 collects: fp32 RGB (the seam's return_image) or the PPM-"
                          "quantised bytes k_shade writes (main.cpp:676-682; 4x fewer bytes over "
                          "xGMI, SURVEY.md 8(f)2).  auto = fp32 on one GPU, u8 when there is a gather")
-    ap.add_argument("--cpu-rows", type=int, default=-1,
+    ap.add_argument("--cpu-rows", type=int, default=None,
                     help="rows of the frame the CPU baseline renders (0 = skip, -1 = as many as a "
-                         "one-row-per-thread probe says fit ~12 s of CPU work)")
+                         "one-row-per-thread probe says fit ~12 s of CPU work; default: -1 with "
+                         "--full, else 0)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo lets several ranks share one GPU to rehearse the N>1 path")
     ap.add_argument("--verify-rows", type=int, default=0,
                     help="N>1: rank 0 checks this many rows of the assembled frame against the "
                          "test oracle after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the two-kernel split, the "
+                         "`linear` leg, the one-frame latency, the `host` leg, the CPU baseline "
+                         "and the BVH `accel` leg (a plain run sets up, warms up, times the K "
+                         "steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes the frame the last timed step computed to DIR as float32 "
+                         ".npy: frame.npy (H, W, 3) when it fits in 64 MB, else frame_sample.npy "
+                         "(n, 3), the pixels at sorted(numpy.random.default_rng(0).choice(H*W, "
+                         "2**21, replace=False)) of the row-major frame")
     return ap.parse_args()
 
 
@@ -301,6 +318,24 @@ def cpu_baseline(scene, eye, look, W, H, shadows, n_rows, gpu_frame):
                   f"({rays} rays, {dt:.1f} s); {how}, row-parallel pthreads",
         "seconds": dt,
     }, same
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE_PIXELS = 1 << 21
+
+
+def dump_frame(frame, W, H, out_dir):
+    """--dump-outputs: the timed path's frame (H*W*3 fp32 values, or the PPM bytes of a u8 gather)
+    as float32 .npy -- whole when it fits the limit, else a fixed seeded sample of its pixels"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    px = frame[:H * W * 3].view(H * W, 3)
+    if H * W * 3 * 4 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), px.float().cpu().numpy().reshape(H, W, 3))
+        return
+    idx = np.sort(np.random.default_rng(0).choice(H * W, DUMP_SAMPLE_PIXELS, replace=False))
+    sample = px[torch.from_numpy(idx).to(px.device)].float().cpu().numpy()
+    np.save(os.path.join(out_dir, "frame_sample.npy"), sample)
 
 
 def main():
@@ -459,6 +494,8 @@ def main():
         step(i, True)
     fence()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:  # before any later leg reuses the buffers
+        dump_frame(local[(a.steps - 1) % n_buf] if world == 1 else frame, W, H, a.dump_outputs)
     if frame_cnt is not None:
         cnt = {k: v * a.steps for k, v in frame_cnt.items()}  # K identical frames
     else:
@@ -470,7 +507,7 @@ def main():
     # per-kernel durations (HIP events recorded by the library between the frame's kernels):
     # a few extra frames outside the timed region, one at a time
     kernel_split = None
-    if world == 1 and a.stage != "bvh":
+    if a.full and world == 1 and a.stage != "bvh":
         acc = [0.0, 0.0]
         n_split = 3
         for _ in range(n_split):
@@ -494,7 +531,7 @@ def main():
     # scratch.
     linear = None
     anyhit_index_order = None
-    n_lin = a.linear_steps if a.linear_steps >= 0 else min(a.steps, 5)
+    n_lin = a.linear_steps if a.linear_steps >= 0 else (min(a.steps, 5) if a.full else 0)
     if world == 1 and a.stage != "bvh" and not a.profile_run and a.path == "culled" and n_lin > 0:
         lin_ev = []
         for i in range(n_lin + 1):
@@ -535,12 +572,14 @@ def main():
                             stage=stage, flags=path_flags)
         r.synchronize()
     # one un-pipelined frame: launch -> complete frame resident on rank 0
-    fence()
-    t1 = time.perf_counter()
-    step(0, False)
-    fence()
-    frame_latency_ms = (time.perf_counter() - t1) * 1e3
-    r.synchronize()
+    frame_latency_ms = None
+    if a.full:
+        fence()
+        t1 = time.perf_counter()
+        step(0, False)
+        fence()
+        frame_latency_ms = (time.perf_counter() - t1) * 1e3
+        r.synchronize()
 
     # (after the last use of the recorded frames: rendering another band rebuilds the tile lists they
     # were recorded with)
@@ -549,7 +588,7 @@ def main():
     # For the whole frame and for rank 0's share of an 8-rank frame (where it matters: that share is
     # a few tens of microseconds of GPU work).
     host = None
-    if world == 1 and a.stage != "bvh":
+    if a.full and world == 1 and a.stage != "bvh":
         host = {"what": "host microseconds per frame, K frames enqueued without waiting: `plain` = "
                         "esc_render_strips (parameter block + one launch per kernel), `recorded` = "
                         "esc_frame_launch (one hipGraphLaunch); through the Python binding",
@@ -757,18 +796,19 @@ def main():
         if pipelined is not None:
             pipelined["value"] = rays / a.steps / (pipelined["ms_per_step"] * 1e-3) / 1e6
             out["pipelined"] = pipelined
-        if world == 1 and a.cpu_rows != 0:
+        cpu_rows = a.cpu_rows if a.cpu_rows is not None else (-1 if a.full else 0)
+        if world == 1 and cpu_rows != 0:
             gpu_frame = None
             if not use_u8:
                 gpu_frame = local[0][:H * W * 3].cpu().numpy().reshape(H, W, 3)
-            cb, same = cpu_baseline(scene, eye, look, W, H, shadows, a.cpu_rows, gpu_frame)
+            cb, same = cpu_baseline(scene, eye, look, W, H, shadows, cpu_rows, gpu_frame)
             out["cpu_baseline"] = cb
             # like for like: the CPU baseline sweeps every pair linearly, as `linear` does
             out["gpu_vs_cpu"] = {
                 "linear_over_cpu": (linear["value"] / cb["value"]) if linear else None,
                 (a.stage if a.stage in ("bvh", "lds") else a.path) + "_over_cpu": out["value"] / cb["value"]}
             out["parity_sample_rows_bit_exact"] = same
-        if world == 1 and a.stage != "bvh" and not a.no_accel and not use_u8:
+        if a.full and world == 1 and a.stage != "bvh" and not a.no_accel and not use_u8:
             out["accel"] = accel_leg(esc, r, st, cam, eye, look, W, H, shadows, a.steps, a.warmup,
                                      local[0], alg_bytes, a.count_every_frame)
         if world > 1 and a.verify_rows > 0:

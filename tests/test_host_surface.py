@@ -21,6 +21,20 @@ def esc():
     return m
 
 
+@pytest.fixture(scope="module")
+def models(tmp_path_factory):
+    """the reference's bundled models (cornell_box.obj and cornell/*.obj + .mtl, CC BY 3.0: see
+    cornell/copyright.txt), stored as tests/golden/cornell_models.tar.gz and unpacked per run"""
+    import tarfile
+    d = tmp_path_factory.mktemp("models")
+    with tarfile.open(os.path.join(ROOT, "tests", "golden", "cornell_models.tar.gz")) as t:
+        if hasattr(tarfile, "data_filter"):
+            t.extractall(d, filter="data")
+        else:
+            t.extractall(d)
+    return str(d)
+
+
 def test_library_exports_every_declared_symbol(esc):
     from esctp1raytracer_amd import _capi
     header = open(os.path.join(ROOT, "include", "esctp1_rt.h")).read()
@@ -165,26 +179,24 @@ def test_loader_on_committed_obj_fixtures(esc, name, golden_dir):
     _assert_same_scene(ol.scene_from_product(sc), ol.load_dump(name))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/models"),
-                    reason="bundled models live in the reference tree only")
 @pytest.mark.parametrize("name", LOADER_DUMPS[2:])
-def test_loader_bit_equal_to_reference_loader_dump(esc, name):
-    """every bundled OBJ the reference can load: geometry split (quirk S11), de-indexing,
-    tinyobj's digit-by-digit float parse, normalised normals, light list"""
+def test_loader_bit_equal_to_reference_loader_dump(esc, name, models):
+    """every bundled OBJ the reference can load (its models, from tests/golden/cornell_models.tar.gz):
+    geometry split (quirk S11), de-indexing, tinyobj's digit-by-digit float parse, normalised
+    normals, light list"""
     sub = "" if name in ("cornell_box",) else "cornell/"
-    sc = esc.Scene.load_obj(f"/root/reference/src/models/{sub}{name}.obj")
+    sc = esc.Scene.load_obj(os.path.join(models, f"{sub}{name}.obj"))
     _assert_same_scene(ol.scene_from_product(sc), ol.load_dump(name))
     if name == "CornellBox-Original":  # S11: short box joins leftWall
         assert [len(g["face_index"]) for g in ol.load_dump(name)["geometry"]] == [2, 2, 2, 2, 14, 12, 2]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/models"), reason="needs bundled models")
-def test_loader_rejects_what_the_reference_rejects(esc, golden_dir):
+def test_loader_rejects_what_the_reference_rejects(esc, golden_dir, models):
     throws = [str(n) for n in np.load(golden_dir + "/loader_throws.npz")["names"]]
     assert sorted(throws) == ["CornellBox-Glossy", "CornellBox-Glossy-Floor"]  # quirk S10
     for n in throws:
         with pytest.raises(esc.EscError) as e:
-            esc.Scene.load_obj(f"/root/reference/src/models/cornell/{n}.obj")
+            esc.Scene.load_obj(os.path.join(models, "cornell", f"{n}.obj"))
         assert e.value.code == -4
 
 
@@ -349,7 +361,7 @@ def test_viewer_cli_surface():
     assert r.returncode != 0 and "Error parsing view" in r.stderr
 
 
-def test_host_code_under_sanitizers(tmp_path, golden_dir):
+def test_host_code_under_sanitizers(tmp_path, golden_dir, models):
     """scene model, loader, synthetic scenes, flatten, PPM writer and BVH builder under ASan + UBSan (CPU
     build of the host half only; the GPU pool offers no sanitizer runs)"""
     exe = tmp_path / "host_sanitize"
@@ -366,9 +378,8 @@ def test_host_code_under_sanitizers(tmp_path, golden_dir):
         pytest.skip("sanitizer runtime not available")
     assert b.returncode == 0, b.stderr[-2000:]
     objs = [os.path.join(golden_dir, "scenes", n) for n in ("one.obj", "two.obj")]
-    if os.path.isdir("/root/reference/src/models/cornell"):
-        objs += sorted(os.path.join("/root/reference/src/models/cornell", f)
-                       for f in os.listdir("/root/reference/src/models/cornell") if f.endswith(".obj"))
+    cornell = os.path.join(models, "cornell")
+    objs += sorted(os.path.join(cornell, f) for f in os.listdir(cornell) if f.endswith(".obj"))
     r = subprocess.run([str(exe)] + objs, capture_output=True, text=True)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     assert "failures=0" in r.stdout and "ERROR: AddressSanitizer" not in r.stderr

@@ -3,14 +3,15 @@
 The reference's host code reaches the render path through ONE header, the ISPC-generated
 `trace_ispc.h` (/root/reference/src/main.cpp:25, src/simplify/flatten_iscp.h:3), and one call,
 `ispc::trace(...)` (main.cpp:619-624).  include/trace_ispc.h is the product's replacement for
-that header.  This test compiles the reference's own main.cpp and flatten_iscp.cpp UNTOUCHED,
-where they lie, against it and links them (plus the other reference objects main.cpp needs)
-with libesctp1rt.so.
+that header.  The oracle build (oracle/Makefile, `ref`) compiles the reference's own main.cpp and
+flatten_iscp.cpp UNTOUCHED, where they lie, against it into oracle/_ref/seam/ (plus the other
+reference objects main.cpp needs); this test links those objects with libesctp1rt.so.
 
 Link only.  The relinked binary is never run: the reference's flatten_scene_ispc leaves
 `ispc_light.light_faces` dangling (flatten_iscp.cpp:39,103, defect I4), so its --ispc path is
 undefined before it reaches `trace` (INTEGRATION.md 1 says what to replace).
-Container only: skipped when /root/reference is absent (the GPU box).  Outputs go to tmp_path.
+The link test skips when oracle/_ref/seam/ was not built (no reference sources at build time).
+Outputs go to tmp_path.
 """
 import os
 import shutil
@@ -19,16 +20,12 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 LIBDIR = os.path.join(ROOT, "esctp1raytracer_amd", "lib")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")),
-                                reason="reference sources not present (GPU box)")
-
-# the reference relies on libc++ transitive includes for INT_MAX,
-# uint32_t and std::string; these are STANDARD headers, nothing of the reference is replaced
-STD_INCLUDES = ["-include", "climits", "-include", "cstdint", "-include", "string"]
-CXXFLAGS = ["-O1", "-std=gnu++17", "-w", "-pthread", f"-I{REF}", f"-I{ROOT}/include"] + STD_INCLUDES
+SEAM = os.path.join(ROOT, "oracle", "_ref", "seam")
+# main.o and flatten_iscp.o include trace_ispc.h -- the seam proper; the rest is the reference's
+# link line (CMakeLists.txt:22 minus the ISPC object)
+SEAM_OBJS = ["main.o", "flatten_iscp.o", "sceneloader.o", "flatten.o", "aabb.o", "bvh.o",
+             "c_vec.o", "c_triangle.o"]
 
 
 def _run(cmd, cwd):
@@ -37,30 +34,16 @@ def _run(cmd, cwd):
     return p
 
 
+@pytest.mark.skipif(not all(os.path.exists(os.path.join(SEAM, o)) for o in SEAM_OBJS),
+                    reason="oracle/_ref/seam not built (needs the reference sources at build time)")
 def test_reference_host_compiles_and_links_against_the_library(tmp_path):
     cxx = shutil.which("g++")
-    cc = shutil.which("gcc")
-    assert cxx and cc
+    assert cxx
     assert os.path.exists(os.path.join(LIBDIR, "libesctp1rt.so"))
-    objs = []
-    # the two translation units that include trace_ispc.h -- the seam proper
-    for src in ("src/main.cpp", "src/simplify/flatten_iscp.cpp"):
-        o = str(tmp_path / (os.path.basename(src) + ".o"))
-        _run([cxx] + CXXFLAGS + ["-c", os.path.join(REF, src), "-o", o], tmp_path)
-        objs.append(o)
+    objs = [os.path.join(SEAM, o) for o in SEAM_OBJS]
     # main.o must reference the plain C symbol `trace` (undefined, to be bound by the library)
     nm = _run(["nm", "-u", objs[0]], tmp_path).stdout.split()
     assert "trace" in nm, "main.cpp does not call the C symbol `trace`"
-    # the rest of the reference's link line (CMakeLists.txt:22 minus the ISPC object)
-    for src in ("src/scene/sceneloader.cpp", "src/simplify/flatten.cpp", "src/scene/aabb.cpp",
-                "src/scene/bvh.cpp"):
-        o = str(tmp_path / (os.path.basename(src) + ".o"))
-        _run([cxx] + CXXFLAGS + ["-c", os.path.join(REF, src), "-o", o], tmp_path)
-        objs.append(o)
-    for src in ("src/simplify/c_vec.c", "src/simplify/c_triangle.c"):
-        o = str(tmp_path / (os.path.basename(src) + ".o"))
-        _run([cc, "-O1", "-w", f"-I{REF}", "-c", os.path.join(REF, src), "-o", o], tmp_path)
-        objs.append(o)
     exe = str(tmp_path / "ESCViewer2021_relinked")
     _run([cxx] + objs + ["-pthread", f"-L{LIBDIR}", "-lesctp1rt", f"-Wl,-rpath,{LIBDIR}",
                          "-Wl,--no-undefined", "-o", exe], tmp_path)

@@ -16,12 +16,12 @@ for P in culled linear; do
   ACC=""; [ $P = linear ] && ACC="--no-accel"
   echo "== [$P] kernel trace + stats"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- \
-    python3 $R/bench.py --config $CFG --path $P --steps 10 --warmup 2 --cpu-rows 0 --profile-run $ACC > $OUT/bench_kt.json 2> $OUT/kt.log || { tail -20 $OUT/kt.log; exit 1; }
+    python3 $R/bench.py --config $CFG --path $P --steps 10 --warmup 2 --cpu-rows 0 --profile-run --full $ACC > $OUT/bench_kt.json 2> $OUT/kt.log || { tail -20 $OUT/kt.log; exit 1; }
   pass() { # name counters...
     local n=$1; shift
     echo "== [$P] pmc $n"
     rocprofv3 --pmc "$@" --output-format csv -d $OUT/pmc_$n -o pmc -- \
-      python3 $R/bench.py --config $CFG --path $P --steps 3 --warmup 1 --cpu-rows 0 --no-accel --profile-run > $OUT/bench_$n.json 2> $OUT/$n.log || { tail -20 $OUT/$n.log; return 1; }
+      python3 $R/bench.py --config $CFG --path $P --steps 3 --warmup 1 --cpu-rows 0 --no-accel --profile-run --full > $OUT/bench_$n.json 2> $OUT/$n.log || { tail -20 $OUT/$n.log; return 1; }
   }
   pass fetch FETCH_SIZE
   pass write WRITE_SIZE
