@@ -384,6 +384,105 @@ class Renderer:
                 "anyhit_lane_tests": c.anyhit_lane_tests}
 
 
+    # ---- batched ray queries (esc_intersect_rays / esc_occluded_rays) --------------------------
+    def _query_ptr(self, name, buf, dtype, shape):
+        import torch
+        if not isinstance(buf, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor on the renderer's device")
+        if buf.dtype != dtype:
+            raise TypeError(f"{name} must be {dtype}, got {buf.dtype}")
+        if tuple(buf.shape) != tuple(shape):
+            raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(buf.shape)}")
+        if not buf.is_cuda or buf.device.index != self.device:
+            raise ValueError(f"{name} must be a device tensor on cuda:{self.device}")
+        if not buf.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        return C.c_void_p(buf.data_ptr())
+
+    def _query_inputs(self, origins, dirs, tmax):
+        import torch
+        if not hasattr(origins, "shape") or len(origins.shape) != 2:
+            raise ValueError("origins must have shape (n, 3)")
+        n = int(origins.shape[0])
+        po = self._query_ptr("origins", origins, torch.float32, (n, 3))
+        pd = self._query_ptr("dirs", dirs, torch.float32, (n, 3))
+        pt = None if tmax is None else self._query_ptr("tmax", tmax, torch.float32, (n,))
+        return n, po, pd, pt
+
+    def intersect_rays(self, origins, dirs, t, geom, prim, *, tmax=None, uv=None, exact=False):
+        """Closest hit of n rays (main.cpp:176-192 with the sphere extension), asynchronous on the
+        renderer's stream.  Contiguous device tensors: origins, dirs (n, 3) float32, tmax (n,)
+        float32 or None (FLT_MAX); outputs t (n,) float32, geom, prim (n,) int32, uv (n, 2) float32
+        or None.  geom / prim: geometry and face of a triangle hit, -1 / k for sphere k, -1 / -1 for
+        a miss (t is then the bound).  exact=True: the reference arithmetic for every pair."""
+        import torch
+        n, po, pd, pt = self._query_inputs(origins, dirs, tmax)
+        args = (self._query_ptr("t", t, torch.float32, (n,)),
+                self._query_ptr("geom", geom, torch.int32, (n,)),
+                self._query_ptr("prim", prim, torch.int32, (n,)),
+                None if uv is None else self._query_ptr("uv", uv, torch.float32, (n, 2)))
+        check(self._lib.esc_intersect_rays(self._h, n, po, pd, pt, *args,
+                                           ESC_RENDER_EXACT_ONLY if exact else 0))
+
+    def occluded_rays(self, origins, dirs, out, *, tmax=None, exact=False):
+        """Occlusion of n rays (main.cpp:314-329 with the sphere extension), asynchronous: out (n,)
+        uint8 receives 1 where some primitive is hit before the bound, else 0."""
+        import torch
+        n, po, pd, pt = self._query_inputs(origins, dirs, tmax)
+        check(self._lib.esc_occluded_rays(self._h, n, po, pd, pt,
+                                          self._query_ptr("out", out, torch.uint8, (n,)),
+                                          ESC_RENDER_EXACT_ONLY if exact else 0))
+
+    def _stage(self, origins, dirs, tmax):
+        import torch
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("origins and dirs must both have shape (n, 3)")
+        dev = torch.device("cuda", self.device)
+        to = torch.from_numpy(o).to(dev)
+        td = torch.from_numpy(d).to(dev)
+        tt = None
+        if tmax is not None:
+            m = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+            if m.shape[0] != o.shape[0]:
+                raise ValueError("tmax must have n entries")
+            tt = torch.from_numpy(m).to(dev)
+        # the copies run on torch's stream, the query on the renderer's: order them
+        torch.cuda.current_stream(dev).synchronize()
+        return to, td, tt
+
+    def intersect(self, origins, dirs, tmax=None, *, exact=False):
+        """Synchronous closest hit of numpy rays: {"t", "geom", "prim", "uv"} as numpy arrays."""
+        import torch
+        to, td, tt = self._stage(origins, dirs, tmax)
+        n = to.shape[0]
+        dev = to.device
+        t = torch.empty(n, dtype=torch.float32, device=dev)
+        geom = torch.empty(n, dtype=torch.int32, device=dev)
+        prim = torch.empty(n, dtype=torch.int32, device=dev)
+        uv = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        self.intersect_rays(to, td, t, geom, prim, tmax=tt, uv=uv, exact=exact)
+        self.synchronize()
+        return {"t": t.cpu().numpy(), "geom": geom.cpu().numpy(), "prim": prim.cpu().numpy(),
+                "uv": uv.cpu().numpy()}
+
+    def occluded(self, origins, dirs, tmax=None, *, exact=False):
+        """Synchronous occlusion of numpy rays: a uint8 array (1 = occluded)."""
+        import torch
+        to, td, tt = self._stage(origins, dirs, tmax)
+        out = torch.empty(to.shape[0], dtype=torch.uint8, device=to.device)
+        self.occluded_rays(to, td, out, tmax=tt, exact=exact)
+        self.synchronize()
+        return out.cpu().numpy()
+
+    def query_stats(self):
+        """Counts of the last query call: rays, exact_rays (rays that took the reference loop),
+        exact_tests ((ray, primitive) pairs that ran the reference arithmetic).  Synchronises."""
+        s = _capi.esc_query_stats()
+        check(self._lib.esc_last_query_stats(self._h, C.byref(s)))
+        return {"rays": s.rays, "exact_rays": s.exact_rays, "exact_tests": s.exact_tests}
+
     def tile_lists(self, which):
         """the lists of the last frame (0 / 1: tile lists of spheres / triangles; 2 / 3: light lists of
         sphere / triangle pair records) -> dict with the

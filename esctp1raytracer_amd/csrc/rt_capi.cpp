@@ -16,6 +16,7 @@
 #include "../host/accel_build.h"
 #include "../host/scene.h"
 #include "rt_device.h"
+#include "rt_query.h"
 #include "rt_tile_math.h"
 
 static_assert(sizeof(esc_bvh_node) == sizeof(esc::BvhNode) && sizeof(esc::BvhNode) == 64,
@@ -42,6 +43,7 @@ extern "C" int esc_launch_render(const esc::RenderParams *p, int stage, int px,
 extern "C" int esc_launch_shade_queue(const esc::RenderParams *p, int li, int last, const int *segs,
                                       int n_segs, uint32_t *ctl, int n_wg, hipStream_t stream);
 extern "C" int esc_launch_primary_only(const esc::RenderParams *p, int px, hipStream_t stream);
+extern "C" int esc_launch_query(const esc::QueryParams *p, int occlusion, hipStream_t stream);
 extern "C" int esc_launch_assemble(const void *gathered, void *frame, size_t rank_pitch_bytes,
                                    int n_ranks, int H, int strip_rows, size_t row_bytes,
                                    hipStream_t stream);
@@ -149,6 +151,8 @@ struct esc_context {
   float *d_img = nullptr;
   uint8_t *d_u8 = nullptr;
   size_t img_cap = 0, u8_cap = 0;
+  // esc_query_stats of the last ray query (rt_query.hip), allocated by the first query
+  unsigned long long *d_qstats = nullptr;
 };
 
 namespace {
@@ -210,6 +214,7 @@ int stage_scene(const esc_scene &scene, Staged &s) {
       const uint32_t *face = &g.face_index[3 * f];
       s.tri.push_back(dev_triangle(&g.vertex[3 * face[0]], &g.vertex[3 * face[1]],
                                    &g.vertex[3 * face[2]], (int)gi));
+      s.tri.back().pad[0] = (int32_t)f; // face index within the geometry: the ray queries' prim
       if (any_normals) {
         esc::DevTriN n;
         std::memset(&n, 0, sizeof(n));
@@ -272,6 +277,7 @@ int stage_flat(int32_t nt, const ispc_triangle *tris, int32_t nl, const ispc_lig
   for (int i = 0; i < nt; i++) {
     const ispc_triangle &t = tris[i];
     s.tri.push_back(dev_triangle(t.vertices[0], t.vertices[1], t.vertices[2], t.geom_id));
+    s.tri.back().pad[0] = i; // index in triangles[]: the ray queries' prim
     esc::DevMat &m = s.mat[(size_t)t.geom_id]; // material is replicated per triangle
     std::memcpy(m.ka, t.ka, 12);
     std::memcpy(m.kd, t.kd, 12);
@@ -1057,7 +1063,7 @@ void esc_context_destroy(esc_context *ctx) {
                   ctx->d_bvh_tri_blocks_p, ctx->d_bvh_sph_blocks_p,
                   ctx->d_tri_boxes, ctx->d_sph_boxes, ctx->d_bin_hdr, ctx->d_bin_tri_ids,
                   ctx->d_bin_sph_ids, ctx->lbins.face_hdr, ctx->lbins.counts, ctx->lbins.tri_ids,
-                  ctx->lbins.sph_ids};
+                  ctx->lbins.sph_ids, ctx->d_qstats};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t ev : ctx->ev)
@@ -2072,6 +2078,107 @@ int esc_last_kernel_ms(esc_context *ctx, float ms[2]) {
   HIP_TRY(hipEventSynchronize(ctx->ev[2]));
   HIP_TRY(hipEventElapsedTime(&ms[0], ctx->ev[0], ctx->ev[1]));
   HIP_TRY(hipEventElapsedTime(&ms[1], ctx->ev[1], ctx->ev[2]));
+  return ESC_OK;
+}
+
+// ---- batched ray queries (rt_query.hip) ---------------------------------------------------
+static int query_launch(esc_context *ctx, const char *fn, bool occ, int64_t n, const float *d_origins,
+                 const float *d_dirs, const float *d_tmax, float *d_t, int32_t *d_geom,
+                 int32_t *d_prim, float *d_uv, uint8_t *d_occ, uint32_t flags) {
+  if (!ctx) {
+    set_error(std::string(fn) + ": ctx is null");
+    return ESC_ERR_INVALID;
+  }
+  if (!ctx->have_scene) {
+    set_error(std::string(fn) + ": no scene uploaded (esc_upload_scene / esc_upload_flat)");
+    return ESC_ERR_INVALID;
+  }
+  if (n < 0) {
+    set_error(std::string(fn) + ": n < 0");
+    return ESC_ERR_INVALID;
+  }
+  if (flags & ~(uint32_t)ESC_RENDER_EXACT_ONLY) {
+    set_error(std::string(fn) + ": flags takes 0 or ESC_RENDER_EXACT_ONLY only");
+    return ESC_ERR_INVALID;
+  }
+  if (n > 0 && (!d_origins || !d_dirs || (occ ? !d_occ : (!d_t || !d_geom || !d_prim)))) {
+    set_error(std::string(fn) + (occ ? ": d_origins, d_dirs and d_occluded are required"
+                                     : ": d_origins, d_dirs, d_t, d_geom and d_prim are required"));
+    return ESC_ERR_INVALID;
+  }
+  const uintptr_t bad = ((uintptr_t)d_origins | (uintptr_t)d_dirs | (uintptr_t)d_tmax |
+                         (uintptr_t)d_t | (uintptr_t)d_geom | (uintptr_t)d_prim | (uintptr_t)d_uv) & 3u;
+  if (bad) {
+    set_error(std::string(fn) + ": device pointers must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error(std::string(fn) + ": n exceeds one launch (2^32 - 1 workgroups of 256 rays)");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!ctx->d_qstats) HIP_TRY(hipMalloc((void **)&ctx->d_qstats, 4 * sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(ctx->d_qstats, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  if (n == 0) return ESC_OK;
+  esc::QueryParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.n = n;
+  p.orig = d_origins;
+  p.dir = d_dirs;
+  p.tmax = d_tmax;
+  p.t = d_t;
+  p.geom = d_geom;
+  p.prim = d_prim;
+  p.uv = d_uv;
+  p.occ = d_occ;
+  p.n_tri = ctx->n_tri;
+  p.n_sph = ctx->n_sph;
+  p.tri = ctx->d_tri;
+  p.sph = ctx->d_sph;
+  p.sph2_f = ctx->d_sph2_f;
+  p.tri2_f = ctx->d_tri2_f;
+  p.tri2_pf = ctx->d_tri2_pf;
+  p.sg = ctx->sg;
+  p.tg = ctx->tg;
+  std::memcpy(p.g, ctx->shadow_center, sizeof(p.g));
+  p.rho_max = ctx->shadow_rho_max;
+  p.exact_only = (flags & ESC_RENDER_EXACT_ONLY) ? 1 : 0;
+  p.stats = ctx->d_qstats;
+  const int e = esc_launch_query(&p, occ ? 1 : 0, ctx->stream);
+  if (e) {
+    set_error(std::string(fn) + ": k_query launch: " + hipGetErrorString((hipError_t)e));
+    return ESC_ERR_HIP;
+  }
+  return ESC_OK;
+}
+
+int esc_intersect_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs,
+                       const float *d_tmax, float *d_t, int32_t *d_geom, int32_t *d_prim,
+                       float *d_uv, uint32_t flags) {
+  return query_launch(ctx, "esc_intersect_rays", false, n, d_origins, d_dirs, d_tmax, d_t, d_geom, d_prim,
+                      d_uv, nullptr, flags);
+}
+
+int esc_occluded_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs,
+                      const float *d_tmax, uint8_t *d_occluded, uint32_t flags) {
+  return query_launch(ctx, "esc_occluded_rays", true, n, d_origins, d_dirs, d_tmax, nullptr, nullptr,
+                      nullptr, nullptr, d_occluded, flags);
+}
+
+int esc_last_query_stats(esc_context *ctx, esc_query_stats *out) {
+  if (!ctx || !out) {
+    set_error(!ctx ? "esc_last_query_stats: ctx is null" : "esc_last_query_stats: out is null");
+    return ESC_ERR_INVALID;
+  }
+  unsigned long long h[4] = {0, 0, 0, 0};
+  if (ctx->d_qstats) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_qstats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  out->rays = h[0];
+  out->exact_rays = h[1];
+  out->exact_tests = h[2];
   return ESC_OK;
 }
 

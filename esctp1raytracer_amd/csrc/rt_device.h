@@ -20,7 +20,8 @@ struct alignas(16) DevTri {
   float e1[3]; // vert1 - vert0
   float e2[3]; // vert2 - vert0
   int32_t geom; // material / geometry id
-  int32_t pad[2];
+  int32_t pad[2]; // pad[0]: face index within the geometry (index in triangles[] for a flat upload),
+                  // set at staging and read only by the ray queries (rt_query.hip)
 };
 
 // Primary rays share one origin (camera.h:32), so tvec, qvec and dot(edge2,qvec)

@@ -106,6 +106,25 @@ DEVINL bool tri_exact_nb(float detf, float unum, float vnum, float tnum, float &
   v2o = v2;
   return true;
 }
+// The same, also returning u2 (ray_triangle.h:32, the same f64 product): the ray queries
+// (rt_query.hip) report both barycentrics.
+DEVINL bool tri_exact_nb_uv(float detf, float unum, float vnum, float tnum, float &t2o, float &u2o,
+                            float &v2o) {
+  const double eps = (double)FLT_EPSILON;
+  double det = (double)detf;                    // :21
+  if (det > -eps && det < eps) return false;    // :23-25
+  double inv_det = 1.0 / det;                   // :26 (1.0f widened)
+  float u2 = (float)((double)unum * inv_det);   // :32
+  if (u2 < FLT_EPSILON || u2 > 1.0f) return false; // :33
+  float v2 = (float)((double)vnum * inv_det);   // :40
+  if (v2 < FLT_EPSILON || u2 + v2 > 1.0f) return false; // :41
+  float t2 = (float)((double)tnum * inv_det);   // :45
+  if (t2 < FLT_EPSILON) return false;           // :46
+  t2o = t2;
+  u2o = u2;
+  v2o = v2;
+  return true;
+}
 // ray_triangle.h:21-54.  Returns true on accept.
 DEVINL bool tri_exact(float detf, float unum, float vnum, float tnum, float tbound, float &t2o,
                       float &v2o) {

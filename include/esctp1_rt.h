@@ -468,6 +468,45 @@ int esc_last_kernel_ms(esc_context *ctx, float ms[2]);
 int esc_reset_counters(esc_context *ctx);
 int esc_read_counters(esc_context *ctx, esc_counters *out);
 
+/* ---- batched ray queries ---------------------------------------------------------------
+ * The reference's two primitive loops on rays of the caller's own (picking, visibility or
+ * ambient-occlusion baking, collision probes, custom shading passes).  Every pointer is a DEVICE
+ * pointer, 4-byte aligned; the calls are asynchronous on the context's stream; n == 0 launches
+ * nothing (and the pointers may then be NULL).  A query reads only the uploaded scene's tables: no
+ * camera state, tile or light lists, render counters or recorded frame is touched.
+ * Results are bit-identical to the reference arithmetic for any float input (non-unit, zero, NaN
+ * or infinite directions, origins anywhere): a ray that is not unit to a few ulp, starts outside
+ * the region the culling bounds were proven for, or has a NaN bound runs the reference loop itself
+ * (counted in esc_query_stats.exact_rays).
+ * flags: 0, or ESC_RENDER_EXACT_ONLY (every pair through the reference arithmetic in index order,
+ * no filters, no groups: the A/B and the tests' reference on large scenes); other bits are
+ * rejected. */
+typedef struct {
+  uint64_t rays;        /* rays of the last query call */
+  uint64_t exact_rays;  /* rays that took the exact sweep (all of them under ESC_RENDER_EXACT_ONLY) */
+  uint64_t exact_tests; /* (ray, primitive) pairs that ran the reference arithmetic */
+} esc_query_stats;
+/* Closest hit == intersect() / cpp_intersect() (main.cpp:176-192, 302-312): per ray, t starts at
+ * d_tmax[i] (NULL: FLT_MAX, main.cpp:715) and intersect_triangle (ray_triangle.h:7-57) runs over
+ * every triangle, geometry by geometry and face by face, then the sphere extension over every
+ * sphere (after every triangle in tie order).  Outputs: d_t[i] (== the bound on a miss),
+ * d_geom[i] / d_prim[i] = geometry index and face index of a triangle hit (for a scene uploaded
+ * with esc_upload_flat: the triangle's geom_id and its index in triangles[]), -1 / k for sphere k,
+ * -1 / -1 for a miss; d_uv (n x 2, may be NULL) = the u2, v2 intersect_triangle writes for the
+ * winning triangle (quirk S1 is the caller's aliasing, main.cpp:307-310, not the function's),
+ * 0 / 0 otherwise.  d_origins, d_dirs: n x 3 floats. */
+int esc_intersect_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs,
+                       const float *d_tmax, float *d_t, int32_t *d_geom, int32_t *d_prim,
+                       float *d_uv, uint32_t flags);
+/* Occlusion == occlusion() (main.cpp:314-329) with the sphere extension: d_occluded[i] = 1 if any
+ * primitive is accepted with t carried from d_tmax[i] (NULL: FLT_MAX), else 0 -- the same answer
+ * as "esc_intersect_rays found a hit". */
+int esc_occluded_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs,
+                      const float *d_tmax, uint8_t *d_occluded, uint32_t flags);
+/* counts of the last query call on this context (zero before the first); synchronises the
+ * context's stream */
+int esc_last_query_stats(esc_context *ctx, esc_query_stats *out);
+
 /* Whole frame into HOST memory, synchronous: render + D2H.  `image` = W*H*3 floats. */
 int esc_render_frame_host(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
                           const esc_render_options *opts, float *image, uint8_t *rgb8);
