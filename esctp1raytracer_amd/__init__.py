@@ -483,6 +483,82 @@ class Renderer:
         check(self._lib.esc_last_query_stats(self._h, C.byref(s)))
         return {"rays": s.rays, "exact_rays": s.exact_rays, "exact_tests": s.exact_tests}
 
+    # ---- shading of caller-supplied rays (esc_camera_rays / esc_shade_rays) -----------------------
+    def camera_rays(self, camera, W, H, rows=None, offsets=None):
+        """The frame's primary rays as device tensors (origins, dirs), each (n, 3) float32, ray
+        (h - r0) * W + w for rows (r0, r1) (None: the whole frame).  offsets: None or a contiguous
+        (n, 2) float32 device tensor of sub-pixel offsets (dx, dy).  Asynchronous."""
+        import torch
+        r0, r1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+        n = max(0, (r1 - r0) * W)
+        dev = torch.device("cuda", self.device)
+        o = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        d = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        po = None if offsets is None else self._query_ptr("offsets", offsets, torch.float32, (n, 2))
+        check(self._lib.esc_camera_rays(self._h, C.byref(camera.c), W, H, r0, r1, po,
+                                        C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr())))
+        return o, d
+
+    def shade_rays(self, origins, dirs, rgb, *, rgb8=None, t=None, geom=None, prim=None, pixel_base=0,
+                   shadows=True, face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False):
+        """scan_row's colour (main.cpp:698-791) of n rays, asynchronous on the renderer's stream.
+        Contiguous device tensors: origins, dirs (n, 3) float32; outputs rgb (n, 3) float32, rgb8
+        (n, 3) uint8 or None, t (n,) float32, geom, prim (n,) int32 or None (esc_intersect_rays's
+        values).  pixel_base: the face_hash pixel index of ray 0.  exact=True: every primary and
+        shadow ray through the reference loop."""
+        import torch
+        n, po, pd, _ = self._query_inputs(origins, dirs, None)
+        args = (self._query_ptr("rgb", rgb, torch.float32, (n, 3)),
+                None if rgb8 is None else self._query_ptr("rgb8", rgb8, torch.uint8, (n, 3)),
+                None if t is None else self._query_ptr("t", t, torch.float32, (n,)),
+                None if geom is None else self._query_ptr("geom", geom, torch.int32, (n,)),
+                None if prim is None else self._query_ptr("prim", prim, torch.int32, (n,)))
+        o = _options(shadows, face_mode, fixed_face, seed, ESC_STAGE_AUTO, 0,
+                     ESC_RENDER_EXACT_ONLY if exact else 0)
+        check(self._lib.esc_shade_rays(self._h, n, po, pd, int(pixel_base) & 0xffffffff, C.byref(o), *args))
+
+    def shade(self, origins, dirs, *, pixel_base=0, shadows=True, face_mode=ESC_FACE_FIXED, fixed_face=0,
+              seed=0, exact=False):
+        """Synchronous shading of numpy rays: {"rgb", "rgb8", "t", "geom", "prim"} as numpy arrays."""
+        import torch
+        to, td, _ = self._stage(origins, dirs, None)
+        n = to.shape[0]
+        dev = to.device
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+        t = torch.empty(n, dtype=torch.float32, device=dev)
+        geom = torch.empty(n, dtype=torch.int32, device=dev)
+        prim = torch.empty(n, dtype=torch.int32, device=dev)
+        self.shade_rays(to, td, rgb, rgb8=rgb8, t=t, geom=geom, prim=prim, pixel_base=pixel_base,
+                        shadows=shadows, face_mode=face_mode, fixed_face=fixed_face, seed=seed, exact=exact)
+        self.synchronize()
+        return {"rgb": rgb.cpu().numpy(), "rgb8": rgb8.cpu().numpy(), "t": t.cpu().numpy(),
+                "geom": geom.cpu().numpy(), "prim": prim.cpu().numpy()}
+
+    def render_supersampled(self, camera, W, H, spp, *, want_u8=False, shadows=True, face_mode=ESC_FACE_FIXED,
+                            fixed_face=0, seed=0, exact=False):
+        """Anti-aliased frame (esc_render_supersampled): spp = n*n samples per pixel, n in 1..8.
+        Returns numpy fp32 (H, W, 3) and optionally the quantised bytes.  Synchronous."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        img = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        u8 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if want_u8 else None
+        o = _options(shadows, face_mode, fixed_face, seed, ESC_STAGE_AUTO, 0,
+                     ESC_RENDER_EXACT_ONLY if exact else 0)
+        torch.cuda.current_stream(dev).synchronize()  # the buffers were made on torch's stream
+        check(self._lib.esc_render_supersampled(self._h, C.byref(camera.c), W, H, int(spp), C.byref(o),
+                                                C.c_void_p(img.data_ptr()),
+                                                None if u8 is None else C.c_void_p(u8.data_ptr())))
+        self.synchronize()
+        return (img.cpu().numpy(), u8.cpu().numpy()) if want_u8 else img.cpu().numpy()
+
+    def shade_stats(self):
+        """Counts of the last shade_rays / render_supersampled call: rays, hit_rays, shadow_rays,
+        exact_rays (primary or shadow rays that took the reference loop), exact_tests.  Synchronises."""
+        s = _capi.esc_shade_stats()
+        check(self._lib.esc_last_shade_stats(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k in ("rays", "hit_rays", "shadow_rays", "exact_rays", "exact_tests")}
+
     def tile_lists(self, which):
         """the lists of the last frame (0 / 1: tile lists of spheres / triangles; 2 / 3: light lists of
         sphere / triangle pair records) -> dict with the

@@ -17,6 +17,7 @@
 #include "../host/scene.h"
 #include "rt_device.h"
 #include "rt_query.h"
+#include "rt_shade_rays.h"
 #include "rt_tile_math.h"
 
 static_assert(sizeof(esc_bvh_node) == sizeof(esc::BvhNode) && sizeof(esc::BvhNode) == 64,
@@ -44,6 +45,10 @@ extern "C" int esc_launch_shade_queue(const esc::RenderParams *p, int li, int la
                                       int n_segs, uint32_t *ctl, int n_wg, hipStream_t stream);
 extern "C" int esc_launch_primary_only(const esc::RenderParams *p, int px, hipStream_t stream);
 extern "C" int esc_launch_query(const esc::QueryParams *p, int occlusion, hipStream_t stream);
+extern "C" int esc_launch_shade_rays(const esc::ShadeParams *p, hipStream_t stream);
+extern "C" int esc_launch_camera_rays(const esc::CameraRayParams *p, hipStream_t stream);
+extern "C" int esc_launch_ss_accumulate(float *acc, const float *rgb, int64_t n, int first, hipStream_t stream);
+extern "C" int esc_launch_ss_finish(float *img, uint8_t *u8, int64_t n, float spp, hipStream_t stream);
 extern "C" int esc_launch_assemble(const void *gathered, void *frame, size_t rank_pitch_bytes,
                                    int n_ranks, int H, int strip_rows, size_t row_bytes,
                                    hipStream_t stream);
@@ -153,6 +158,11 @@ struct esc_context {
   size_t img_cap = 0, u8_cap = 0;
   // esc_query_stats of the last ray query (rt_query.hip), allocated by the first query
   unsigned long long *d_qstats = nullptr;
+  // esc_shade_stats of the last esc_shade_rays call (rt_shade_rays.hip), allocated by the first one
+  unsigned long long *d_sstats = nullptr;
+  // esc_render_supersampled: one band's rays and colours (grow-only, at most kSsScratchBytes)
+  float *d_ss = nullptr;
+  size_t ss_rays = 0;
 };
 
 namespace {
@@ -1063,7 +1073,7 @@ void esc_context_destroy(esc_context *ctx) {
                   ctx->d_bvh_tri_blocks_p, ctx->d_bvh_sph_blocks_p,
                   ctx->d_tri_boxes, ctx->d_sph_boxes, ctx->d_bin_hdr, ctx->d_bin_tri_ids,
                   ctx->d_bin_sph_ids, ctx->lbins.face_hdr, ctx->lbins.counts, ctx->lbins.tri_ids,
-                  ctx->lbins.sph_ids, ctx->d_qstats};
+                  ctx->lbins.sph_ids, ctx->d_qstats, ctx->d_sstats, ctx->d_ss};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t ev : ctx->ev)
@@ -2082,6 +2092,21 @@ int esc_last_kernel_ms(esc_context *ctx, float ms[2]) {
 }
 
 // ---- batched ray queries (rt_query.hip) ---------------------------------------------------
+// the per-scene tables every sweep of rt_query_sweep.h reads
+static void query_tables(const esc_context *ctx, esc::QueryParams &p) {
+  p.n_tri = ctx->n_tri;
+  p.n_sph = ctx->n_sph;
+  p.tri = ctx->d_tri;
+  p.sph = ctx->d_sph;
+  p.sph2_f = ctx->d_sph2_f;
+  p.tri2_f = ctx->d_tri2_f;
+  p.tri2_pf = ctx->d_tri2_pf;
+  p.sg = ctx->sg;
+  p.tg = ctx->tg;
+  std::memcpy(p.g, ctx->shadow_center, sizeof(p.g));
+  p.rho_max = ctx->shadow_rho_max;
+}
+
 static int query_launch(esc_context *ctx, const char *fn, bool occ, int64_t n, const float *d_origins,
                  const float *d_dirs, const float *d_tmax, float *d_t, int32_t *d_geom,
                  int32_t *d_prim, float *d_uv, uint8_t *d_occ, uint32_t flags) {
@@ -2131,17 +2156,7 @@ static int query_launch(esc_context *ctx, const char *fn, bool occ, int64_t n, c
   p.prim = d_prim;
   p.uv = d_uv;
   p.occ = d_occ;
-  p.n_tri = ctx->n_tri;
-  p.n_sph = ctx->n_sph;
-  p.tri = ctx->d_tri;
-  p.sph = ctx->d_sph;
-  p.sph2_f = ctx->d_sph2_f;
-  p.tri2_f = ctx->d_tri2_f;
-  p.tri2_pf = ctx->d_tri2_pf;
-  p.sg = ctx->sg;
-  p.tg = ctx->tg;
-  std::memcpy(p.g, ctx->shadow_center, sizeof(p.g));
-  p.rho_max = ctx->shadow_rho_max;
+  query_tables(ctx, p);
   p.exact_only = (flags & ESC_RENDER_EXACT_ONLY) ? 1 : 0;
   p.stats = ctx->d_qstats;
   const int e = esc_launch_query(&p, occ ? 1 : 0, ctx->stream);
@@ -2179,6 +2194,265 @@ int esc_last_query_stats(esc_context *ctx, esc_query_stats *out) {
   out->rays = h[0];
   out->exact_rays = h[1];
   out->exact_tests = h[2];
+  return ESC_OK;
+}
+
+// ---- shading of caller-supplied rays, camera rays, supersampling (rt_shade_rays.hip) ---------------
+// scratch of esc_render_supersampled: origins, directions and colours of one band (36 B per ray)
+constexpr size_t kSsScratchBytes = size_t(256) << 20;
+constexpr int kShadeStats = 5;
+
+static int shade_options_ok(const esc_context *ctx, const char *fn, const esc_render_options *opts) {
+  if (opts->flags & ~(int32_t)ESC_RENDER_EXACT_ONLY) {
+    set_error(std::string(fn) + ": flags takes 0 or ESC_RENDER_EXACT_ONLY only");
+    return ESC_ERR_INVALID;
+  }
+  if (opts->stage != ESC_STAGE_AUTO) {
+    set_error(std::string(fn) + ": stage must be ESC_STAGE_AUTO");
+    return ESC_ERR_INVALID;
+  }
+  if (opts->face_mode != ESC_FACE_FIXED && opts->face_mode != ESC_FACE_HASH) {
+    set_error(std::string(fn) + ": face_mode must be ESC_FACE_FIXED or ESC_FACE_HASH");
+    return ESC_ERR_INVALID;
+  }
+  if (opts->face_mode == ESC_FACE_FIXED &&
+      (opts->fixed_face < 0 || (ctx->n_lights > 0 && opts->fixed_face >= ctx->min_light_faces))) {
+    // main.cpp:743-748 draws faceID in [0, light.face_index.size())
+    set_error(std::string(fn) + ": fixed_face must be in [0, face count of the smallest light)");
+    return ESC_ERR_INVALID;
+  }
+  return ESC_OK;
+}
+
+static int shade_stats_reset(esc_context *ctx) {
+  if (!ctx->d_sstats) HIP_TRY(hipMalloc((void **)&ctx->d_sstats, kShadeStats * sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(ctx->d_sstats, 0, kShadeStats * sizeof(unsigned long long), ctx->stream));
+  return ESC_OK;
+}
+
+// k_shade_rays on n rays; the caller has validated everything and reset the stats
+static int shade_launch(esc_context *ctx, const char *fn, int64_t n, const float *d_origins, const float *d_dirs,
+                        uint32_t pixel_base, const esc_render_options *opts, uint64_t seed, float *d_rgb,
+                        uint8_t *d_rgb8, float *d_t, int32_t *d_geom, int32_t *d_prim) {
+  if (n == 0) return ESC_OK;
+  esc::ShadeParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.q.n = n;
+  p.q.orig = d_origins;
+  p.q.dir = d_dirs;
+  query_tables(ctx, p.q);
+  p.q.exact_only = (opts->flags & ESC_RENDER_EXACT_ONLY) ? 1 : 0;
+  p.rgb = d_rgb;
+  p.rgb8 = d_rgb8;
+  p.t = d_t;
+  p.geom = d_geom;
+  p.prim = d_prim;
+  p.tri_n = ctx->d_tri_n;
+  p.mat = ctx->d_mat;
+  p.sph_mat = ctx->d_sph_mat;
+  p.lights = ctx->d_lights;
+  p.light_points = ctx->d_light_points;
+  p.n_lights = ctx->n_lights;
+  p.shadows = opts->shadows ? 1 : 0;
+  p.face_mode = opts->face_mode;
+  p.fixed_face = opts->fixed_face;
+  p.seed = seed;
+  p.pixel_base = pixel_base;
+  p.stats = ctx->d_sstats;
+  const int e = esc_launch_shade_rays(&p, ctx->stream);
+  if (e) {
+    set_error(std::string(fn) + ": k_shade_rays launch: " + hipGetErrorString((hipError_t)e));
+    return ESC_ERR_HIP;
+  }
+  return ESC_OK;
+}
+
+static int camera_launch(esc_context *ctx, const char *fn, const esc_camera *cam, int32_t W, int32_t H,
+                         int64_t pix0, int64_t n, const float *d_offsets, float dx, float dy, float *d_origins,
+                         float *d_dirs) {
+  if (n == 0) return ESC_OK;
+  esc::CameraRayParams p;
+  std::memset(&p, 0, sizeof(p));
+  std::memcpy(p.origin, cam->origin, 12);
+  std::memcpy(p.llc, cam->lower_left_corner, 12);
+  std::memcpy(p.horizontal, cam->horizontal, 12);
+  std::memcpy(p.vertical, cam->vertical, 12);
+  p.W = W;
+  p.H = H;
+  p.pix0 = pix0;
+  p.n = n;
+  p.offsets = d_offsets;
+  p.dx = dx;
+  p.dy = dy;
+  p.orig = d_origins;
+  p.dir = d_dirs;
+  const int e = esc_launch_camera_rays(&p, ctx->stream);
+  if (e) {
+    set_error(std::string(fn) + ": k_camera_rays launch: " + hipGetErrorString((hipError_t)e));
+    return ESC_ERR_HIP;
+  }
+  return ESC_OK;
+}
+
+int esc_camera_rays(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t row_begin,
+                    int32_t row_end, const float *d_offsets, float *d_origins, float *d_dirs) {
+  const char *fn = "esc_camera_rays";
+  if (!ctx || !cam) {
+    set_error(!ctx ? "esc_camera_rays: ctx is null" : "esc_camera_rays: cam is null");
+    return ESC_ERR_INVALID;
+  }
+  if (W < 2 || H < 2 || row_begin < 0 || row_end > H || row_begin > row_end) {
+    set_error("esc_camera_rays: need W,H >= 2 and 0 <= row_begin <= row_end <= H");
+    return ESC_ERR_INVALID;
+  }
+  const int64_t n = (int64_t)(row_end - row_begin) * W;
+  if (n > 0 && (!d_origins || !d_dirs)) {
+    set_error("esc_camera_rays: d_origins and d_dirs are required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_offsets | (uintptr_t)d_origins | (uintptr_t)d_dirs) & 3u) {
+    set_error("esc_camera_rays: device pointers must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error("esc_camera_rays: too many rays for one launch");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  return camera_launch(ctx, fn, cam, W, H, (int64_t)row_begin * W, n, d_offsets, 0.f, 0.f, d_origins, d_dirs);
+}
+
+int esc_shade_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs, uint32_t pixel_base,
+                   const esc_render_options *opts, float *d_rgb, uint8_t *d_rgb8, float *d_t, int32_t *d_geom,
+                   int32_t *d_prim) {
+  const char *fn = "esc_shade_rays";
+  if (!ctx || !opts) {
+    set_error(!ctx ? "esc_shade_rays: ctx is null" : "esc_shade_rays: opts is null");
+    return ESC_ERR_INVALID;
+  }
+  if (!ctx->have_scene) {
+    set_error("esc_shade_rays: no scene uploaded (esc_upload_scene / esc_upload_flat)");
+    return ESC_ERR_INVALID;
+  }
+  if (n < 0) {
+    set_error("esc_shade_rays: n < 0");
+    return ESC_ERR_INVALID;
+  }
+  int rc = shade_options_ok(ctx, fn, opts);
+  if (rc) return rc;
+  if (n > 0 && (!d_origins || !d_dirs || !d_rgb)) {
+    set_error("esc_shade_rays: d_origins, d_dirs and d_rgb are required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_origins | (uintptr_t)d_dirs | (uintptr_t)d_rgb | (uintptr_t)d_t | (uintptr_t)d_geom |
+       (uintptr_t)d_prim) & 3u) {
+    set_error("esc_shade_rays: device pointers must be 4-byte aligned (d_rgb8 excepted)");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error("esc_shade_rays: n exceeds one launch (2^32 - 1 workgroups of 256 rays)");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  if ((rc = shade_stats_reset(ctx))) return rc;
+  return shade_launch(ctx, fn, n, d_origins, d_dirs, pixel_base, opts, opts->seed, d_rgb, d_rgb8, d_t, d_geom,
+                      d_prim);
+}
+
+int esc_last_shade_stats(esc_context *ctx, esc_shade_stats *out) {
+  if (!ctx || !out) {
+    set_error(!ctx ? "esc_last_shade_stats: ctx is null" : "esc_last_shade_stats: out is null");
+    return ESC_ERR_INVALID;
+  }
+  unsigned long long h[kShadeStats] = {0, 0, 0, 0, 0};
+  if (ctx->d_sstats) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_sstats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  out->rays = h[0];
+  out->hit_rays = h[1];
+  out->shadow_rays = h[2];
+  out->exact_rays = h[3];
+  out->exact_tests = h[4];
+  return ESC_OK;
+}
+
+int esc_render_supersampled(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
+                            const esc_render_options *opts, float *d_image, uint8_t *d_u8) {
+  const char *fn = "esc_render_supersampled";
+  if (!ctx || !cam || !opts || !d_image) {
+    set_error(!ctx ? "esc_render_supersampled: ctx is null" : "esc_render_supersampled: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  int nn = 0;
+  for (int k = 1; k <= 8; ++k)
+    if (k * k == spp) nn = k;
+  if (!nn) {
+    set_error("esc_render_supersampled: spp must be n*n with n in 1..8");
+    return ESC_ERR_INVALID;
+  }
+  if (W < 2 || H < 2) {
+    set_error("esc_render_supersampled: need W,H >= 2");
+    return ESC_ERR_INVALID;
+  }
+  if ((int64_t)W * H > 0x7fffffffLL) {
+    set_error("esc_render_supersampled: W*H exceeds the reference's int pixel index (main.cpp:784)");
+    return ESC_ERR_INVALID;
+  }
+  if (!ctx->have_scene) {
+    set_error("esc_render_supersampled: no scene uploaded");
+    return ESC_ERR_INVALID;
+  }
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(cam->origin[k]) || !std::isfinite(cam->lower_left_corner[k]) ||
+        !std::isfinite(cam->horizontal[k]) || !std::isfinite(cam->vertical[k])) {
+      set_error("esc_render_supersampled: camera is not finite");
+      return ESC_ERR_INVALID;
+    }
+  int rc = shade_options_ok(ctx, fn, opts);
+  if (rc) return rc;
+  if (((uintptr_t)d_image) & 3u) {
+    set_error("esc_render_supersampled: d_image must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  // bands of whole rows (of pixels when one row does not fit) within the scratch budget
+  const int64_t total = (int64_t)W * H;
+  int64_t band = std::min<int64_t>(total, (int64_t)(kSsScratchBytes / (9 * sizeof(float))));
+  if (band >= W) band -= band % W;
+  if (ctx->ss_rays < (size_t)band) {
+    if (ctx->d_ss) HIP_TRY(hipFree(ctx->d_ss));
+    ctx->d_ss = nullptr;
+    ctx->ss_rays = 0;
+    HIP_TRY(hipMalloc((void **)&ctx->d_ss, (size_t)band * 9 * sizeof(float)));
+    ctx->ss_rays = (size_t)band;
+  }
+  float *d_o = ctx->d_ss, *d_d = ctx->d_ss + 3 * (size_t)band, *d_rgb = ctx->d_ss + 6 * (size_t)band;
+  if ((rc = shade_stats_reset(ctx))) return rc;
+  for (int64_t p0 = 0; p0 < total; p0 += band) {
+    const int64_t n = std::min(band, total - p0);
+    float *img = d_image + 3 * p0;
+    for (int k = 0; k < spp; ++k) {
+      // sample k = j*n + i at (i + 1/2)/n - 1/2, (j + 1/2)/n - 1/2 pixels (fp32)
+      const float dx = ((float)(k % nn) + 0.5f) / (float)nn - 0.5f;
+      const float dy = ((float)(k / nn) + 0.5f) / (float)nn - 0.5f;
+      if ((rc = camera_launch(ctx, fn, cam, W, H, p0, n, nullptr, dx, dy, d_o, d_d))) return rc;
+      if ((rc = shade_launch(ctx, fn, n, d_o, d_d, (uint32_t)p0, opts, opts->seed + (uint64_t)k, d_rgb, nullptr,
+                             nullptr, nullptr, nullptr)))
+        return rc;
+      const int e = esc_launch_ss_accumulate(img, d_rgb, 3 * n, k == 0 ? 1 : 0, ctx->stream);
+      if (e) {
+        set_error(std::string(fn) + ": k_ss_accumulate launch: " + hipGetErrorString((hipError_t)e));
+        return ESC_ERR_HIP;
+      }
+    }
+    const int e = esc_launch_ss_finish(img, d_u8 ? d_u8 + 3 * p0 : nullptr, 3 * n, (float)spp, ctx->stream);
+    if (e) {
+      set_error(std::string(fn) + ": k_ss_finish launch: " + hipGetErrorString((hipError_t)e));
+      return ESC_ERR_HIP;
+    }
+  }
   return ESC_OK;
 }
 

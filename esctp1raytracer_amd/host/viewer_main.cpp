@@ -28,6 +28,9 @@
 //   --scene c2|c3|c4|c5[:n]   synthetic BASELINE.json workload instead of -m
 //   --shadows 0|1  --seed S  --face K   light-face choice: hashed (default) or fixed K
 //   --dump-f32 path           raw fp32 RGB framebuffer, (h*W+w)*3 order, h = 0 bottom
+//   --spp N       anti-aliased frame: N = n*n samples per pixel on a regular sub-pixel grid, n in 1..8
+//                 (esc_render_supersampled; one GPU, not with --ispc or --bvh).  The frame is the mean
+//                 of the samples; the PPM is written as usual
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +39,8 @@
 #include <iostream>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "esctp1_rt.h"
 
@@ -69,7 +74,7 @@ int main(int argc, char *argv[]) {
   int debug = 1; // INFO, debug.h:3
   float eye[3] = {0, 1, 3}, look[3] = {0, 1, 0}; // main.cpp:426
   int W = 1024, H = 768;                         // main.cpp:427
-  int gpus = 1, shadows = 1, fixed_face = -1;
+  int gpus = 1, shadows = 1, fixed_face = -1, spp = 0;
   unsigned long long seed = 0;
 
   for (int arg = 1; arg < argc; arg++) {
@@ -102,11 +107,25 @@ int main(int argc, char *argv[]) {
     if (a == "--shadows") { if (!next) die("--shadows needs 0|1"); shadows = std::atoi(next); arg++; continue; }
     if (a == "--seed") { if (!next) die("--seed needs S"); seed = std::strtoull(next, nullptr, 0); arg++; continue; }
     if (a == "--face") { if (!next) die("--face needs K"); fixed_face = std::atoi(next); arg++; continue; }
+    if (a == "--spp") {
+      if (!next) die("--spp needs N");
+      char *end = nullptr;
+      const long v = std::strtol(next, &end, 10);
+      int root = 0;
+      for (int k = 1; k <= 8; k++)
+        if (k * k == v) root = k;
+      if (end == next || *end != '\0' || root == 0)
+        die(std::string("--spp must be a square number from 1 to 64 (1, 4, 9, ..., 64), got ") + next);
+      spp = (int)v;
+      arg++;
+      continue;
+    }
     if (a == "--dump-f32") { if (!next) die("--dump-f32 needs a path"); dumpname = next; arg++; continue; }
     die("Invalid Argument: " + a); // main.cpp:531-534
   }
   if (W < 2 || H < 2) die("window must be at least 2x2");
   if (gpus < 1) die("--gpus must be >= 1");
+  if (spp && (ispc || flat || gpus != 1)) die("--spp renders on one GPU and not with --ispc, --bvh or --bvh-tree");
 
   esc_scene *scene = esc_scene_new();
   if (!scene) die("out of memory");
@@ -191,6 +210,17 @@ int main(int argc, char *argv[]) {
                 << "\n num_light_faces = " << nlt << std::endl;
     trace(W, H, &icam, nt, tris, nl, lights, nlt, ltris, image.data(), debug, 0);
     esc_flat_free(fs);
+  } else if (ctx && spp) {
+    // device framebuffer of esc_render_supersampled, copied back like esc_render_frame_host's
+    esc_render_options so = opts;
+    so.flags = 0;
+    float *d_image = nullptr;
+    if (hipMalloc((void **)&d_image, image.size() * sizeof(float)) != hipSuccess) die("out of device memory");
+    check(esc_render_supersampled(ctx, &cam, W, H, spp, &so, d_image, nullptr), "render");
+    check(esc_context_synchronize(ctx), "render");
+    if (hipMemcpy(image.data(), d_image, image.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+      die("copy back failed");
+    (void)hipFree(d_image);
   } else if (ctx) {
     check(esc_render_frame_host(ctx, &cam, W, H, &opts, image.data(), nullptr), "render");
   } else {

@@ -507,6 +507,59 @@ int esc_occluded_rays(esc_context *ctx, int64_t n, const float *d_origins, const
  * context's stream */
 int esc_last_query_stats(esc_context *ctx, esc_query_stats *out);
 
+/* ---- shading of caller-supplied rays, camera rays, supersampled frames ----------------------
+ * scan_row's body (main.cpp:698-791) on rays the caller supplies: any camera model, several samples
+ * per pixel.  Same conventions as the queries above: DEVICE pointers, 4-byte aligned (byte outputs
+ * excepted), asynchronous on the context's stream, n == 0 launches nothing, only the uploaded scene's
+ * tables are read (no camera state, tile or light lists, render counters or recorded frame), and the
+ * results are bit-identical to the reference arithmetic for any float input.
+ *
+ * Primary rays of the frame as data == camera.h:31-34 get_ray as main.cpp:709-713 calls it: ray
+ * i = (h - row_begin)*W + w of rows [row_begin, row_end) has origin cam.origin and direction
+ * normalize(((llc + horizontal*s) + vertical*t) - origin), s = (float(w) + dx) / float(W-1),
+ * t = (float(h) + dy) / float(H-1), (dx, dy) = d_offsets[2i], d_offsets[2i+1] in pixels (NULL: 0).
+ * With no offsets these are, bit for bit, the rays esc_render_rows traces.  d_origins, d_dirs: n x 3
+ * floats, n = (row_end - row_begin)*W.  Needs W,H >= 2. */
+int esc_camera_rays(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t row_begin,
+                    int32_t row_end, const float *d_offsets, float *d_origins, float *d_dirs);
+/* counts of the last esc_shade_rays / esc_render_supersampled call (a NEW struct: esc_query_stats
+ * keeps its layout) */
+typedef struct {
+  uint64_t rays;        /* rays shaded */
+  uint64_t hit_rays;    /* rays whose closest hit found a primitive (main.cpp:722) */
+  uint64_t shadow_rays; /* occlusion() calls (main.cpp:772; 0 when shadows == 0) */
+  uint64_t exact_rays;  /* primary or shadow rays that took the index-order reference loop */
+  uint64_t exact_tests; /* (ray, primitive) pairs that ran the reference arithmetic */
+} esc_shade_stats;
+/* main.cpp:698-791 for each ray (o, d) = (d_origins[i], d_dirs[i]), n x 3 floats each:
+ *   - closest hit with t from FLT_MAX (main.cpp:715-722): d_t, d_geom, d_prim (each NULL or n) equal
+ *     esc_intersect_rays on the same ray;
+ *   - the normal (main.cpp:723-738): face normal, then vertex normals with u == 0 (quirk S1); spheres
+ *     normalize((o + d*t) - C) with the ray's own o;
+ *   - per light in order (main.cpp:740-789): the light sample of quirk S2 (face fixed_face under
+ *     ESC_FACE_FIXED, face_hash(seed, pixel_base + i mod 2^32, light, n_faces) under ESC_FACE_HASH),
+ *     hit = o + d*(t - FLT_EPSILON), t = len - FLT_EPSILON, occlusion() with that t -- the occluder
+ *     of the lowest index, whose t2 the next light starts from (quirk S3) -- and Phong.
+ * d_rgb (n x 3, required) receives the colour, d_rgb8 (n x 3 bytes, or NULL) the PPM quantisation of
+ * main.cpp:676-682.  opts: shadows (0 = primary only), face_mode, fixed_face, seed and flags (0 or
+ * ESC_RENDER_EXACT_ONLY: every primary and shadow ray through the reference loop in index order);
+ * stage must be ESC_STAGE_AUTO, other flags are rejected, pixels_per_lane is ignored.  A primary or
+ * shadow ray outside the filters' preconditions (see the queries above) runs the reference loop. */
+int esc_shade_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs, uint32_t pixel_base,
+                   const esc_render_options *opts, float *d_rgb, uint8_t *d_rgb8, float *d_t, int32_t *d_geom,
+                   int32_t *d_prim);
+/* synchronises the context's stream */
+int esc_last_shade_stats(esc_context *ctx, esc_shade_stats *out);
+/* Anti-aliased frame: spp = n*n samples per pixel (n in 1..8) on a regular grid.  Sample k = j*n + i
+ * is the frame's ray through (w + dx, h + dy), dx = (i + 0.5f)/n - 0.5f, dy = (j + 0.5f)/n - 0.5f
+ * (fp32), shaded by esc_shade_rays with pixel index h*W + w and seed opts.seed + k.  Per pixel and
+ * channel acc = 0; acc += rgb_k for k = 0 .. spp-1 (fp32, in that order); d_image = acc / float(spp)
+ * and d_u8 (or NULL) = its quantisation (main.cpp:676-682).  spp == 1 is esc_render_rows over the
+ * whole frame, bit for bit.  d_image: W*H*3 floats, the layout of esc_render_rows.  Works in bands of
+ * rows with at most 256 MB of scratch.  Asynchronous. */
+int esc_render_supersampled(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
+                            const esc_render_options *opts, float *d_image, uint8_t *d_u8);
+
 /* Whole frame into HOST memory, synchronous: render + D2H.  `image` = W*H*3 floats. */
 int esc_render_frame_host(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
                           const esc_render_options *opts, float *image, uint8_t *rgb8);
