@@ -559,6 +559,62 @@ class Renderer:
         check(self._lib.esc_last_shade_stats(self._h, C.byref(s)))
         return {k: getattr(s, k) for k in ("rays", "hit_rays", "shadow_rays", "exact_rays", "exact_tests")}
 
+    def trace_rays(self, origins, dirs, rgb, *, max_depth, bias, rgb8=None, pixel_base=0, shadows=True,
+                   face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False):
+        """Mirror reflections (esc_trace_rays): shade_rays' colour plus up to max_depth (0..16) specular
+        bounces weighted by the materials' ks; bias >= 0 moves a bounce's origin off its surface.
+        Asynchronous on the renderer's stream, one launch per depth level.  Contiguous device tensors
+        as for shade_rays; max_depth=0 is shade_rays bit for bit."""
+        import torch
+        n, po, pd, _ = self._query_inputs(origins, dirs, None)
+        args = (self._query_ptr("rgb", rgb, torch.float32, (n, 3)),
+                None if rgb8 is None else self._query_ptr("rgb8", rgb8, torch.uint8, (n, 3)))
+        o = _options(shadows, face_mode, fixed_face, seed, ESC_STAGE_AUTO, 0,
+                     ESC_RENDER_EXACT_ONLY if exact else 0)
+        check(self._lib.esc_trace_rays(self._h, n, po, pd, int(pixel_base) & 0xffffffff, C.byref(o),
+                                       int(max_depth), float(bias), *args))
+
+    def trace(self, origins, dirs, *, max_depth, bias, pixel_base=0, shadows=True, face_mode=ESC_FACE_FIXED,
+              fixed_face=0, seed=0, exact=False):
+        """Synchronous tracing of numpy rays: {"rgb", "rgb8"} as numpy arrays."""
+        import torch
+        to, td, _ = self._stage(origins, dirs, None)
+        n = to.shape[0]
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=to.device)
+        rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=to.device)
+        self.trace_rays(to, td, rgb, max_depth=max_depth, bias=bias, rgb8=rgb8, pixel_base=pixel_base,
+                        shadows=shadows, face_mode=face_mode, fixed_face=fixed_face, seed=seed, exact=exact)
+        self.synchronize()
+        return {"rgb": rgb.cpu().numpy(), "rgb8": rgb8.cpu().numpy()}
+
+    def render_traced(self, camera, W, H, *, spp=1, max_depth, bias, want_u8=False, shadows=True,
+                      face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False):
+        """Frame with mirror reflections (esc_render_traced): render_supersampled's samples, each
+        traced through up to max_depth bounces.  Returns numpy fp32 (H, W, 3) and optionally the
+        quantised bytes.  Synchronous."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        img = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        u8 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if want_u8 else None
+        o = _options(shadows, face_mode, fixed_face, seed, ESC_STAGE_AUTO, 0,
+                     ESC_RENDER_EXACT_ONLY if exact else 0)
+        torch.cuda.current_stream(dev).synchronize()  # the buffers were made on torch's stream
+        check(self._lib.esc_render_traced(self._h, C.byref(camera.c), W, H, int(spp), int(max_depth),
+                                          float(bias), C.byref(o), C.c_void_p(img.data_ptr()),
+                                          None if u8 is None else C.c_void_p(u8.data_ptr())))
+        self.synchronize()
+        return (img.cpu().numpy(), u8.cpu().numpy()) if want_u8 else img.cpu().numpy()
+
+    def trace_stats(self):
+        """Counts of the last trace_rays / render_traced call: rays (primary and bounce), hit_rays,
+        shadow_rays, exact_rays, exact_tests and depth_rays (17 values: the rays shaded at each
+        level).  Synchronises."""
+        s = _capi.esc_trace_stats()
+        check(self._lib.esc_last_trace_stats(self._h, C.byref(s)))
+        out = {k: getattr(s, k) for k in ("rays", "hit_rays", "shadow_rays", "exact_rays", "exact_tests")}
+        out["depth_rays"] = [int(v) for v in s.depth_rays]
+        return out
+
     def tile_lists(self, which):
         """the lists of the last frame (0 / 1: tile lists of spheres / triangles; 2 / 3: light lists of
         sphere / triangle pair records) -> dict with the

@@ -94,6 +94,11 @@ class esc_shade_stats(C.Structure):
                 ("exact_rays", C.c_uint64), ("exact_tests", C.c_uint64)]
 
 
+class esc_trace_stats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("hit_rays", C.c_uint64), ("shadow_rays", C.c_uint64),
+                ("exact_rays", C.c_uint64), ("exact_tests", C.c_uint64), ("depth_rays", C.c_uint64 * 17)]
+
+
 class esc_bvh_node(C.Structure):  # 64 bytes
     _fields_ = [("lo0", C.c_float * 3), ("hi0", C.c_float * 3), ("lo1", C.c_float * 3),
                 ("hi1", C.c_float * 3), ("child", C.c_int32 * 2), ("minkey", C.c_uint32 * 2)]
@@ -187,6 +192,11 @@ SIGNATURES = {
     "esc_last_shade_stats": (C.c_int, [_P, C.POINTER(esc_shade_stats)]),
     "esc_render_supersampled": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
                                           C.c_int32, C.POINTER(esc_render_options), _P, _P]),
+    "esc_trace_rays": (C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, C.POINTER(esc_render_options),
+                                 C.c_int32, C.c_float, _P, _P]),
+    "esc_render_traced": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_float, C.POINTER(esc_render_options), _P, _P]),
+    "esc_last_trace_stats": (C.c_int, [_P, C.POINTER(esc_trace_stats)]),
     "esc_render_frame_host": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
                                         C.POINTER(esc_render_options), _F, _U8]),
     "esc_render_frame_multi": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,

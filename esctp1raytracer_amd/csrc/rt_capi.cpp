@@ -18,6 +18,7 @@
 #include "rt_device.h"
 #include "rt_query.h"
 #include "rt_shade_rays.h"
+#include "rt_trace.h"
 #include "rt_tile_math.h"
 
 static_assert(sizeof(esc_bvh_node) == sizeof(esc::BvhNode) && sizeof(esc::BvhNode) == 64,
@@ -49,6 +50,7 @@ extern "C" int esc_launch_shade_rays(const esc::ShadeParams *p, hipStream_t stre
 extern "C" int esc_launch_camera_rays(const esc::CameraRayParams *p, hipStream_t stream);
 extern "C" int esc_launch_ss_accumulate(float *acc, const float *rgb, int64_t n, int first, hipStream_t stream);
 extern "C" int esc_launch_ss_finish(float *img, uint8_t *u8, int64_t n, float spp, hipStream_t stream);
+extern "C" int esc_launch_trace_level(const esc::TraceParams *p, hipStream_t stream);
 extern "C" int esc_launch_assemble(const void *gathered, void *frame, size_t rank_pitch_bytes,
                                    int n_ranks, int H, int strip_rows, size_t row_bytes,
                                    hipStream_t stream);
@@ -163,6 +165,11 @@ struct esc_context {
   // esc_render_supersampled: one band's rays and colours (grow-only, at most kSsScratchBytes)
   float *d_ss = nullptr;
   size_t ss_rays = 0;
+  // esc_trace_rays / esc_render_traced (rt_trace.hip): esc_trace_stats + the queue counters, and one
+  // batch's queues (plus, for a frame, its rays and colours); grow-only, at most kSsScratchBytes
+  unsigned long long *d_tstats = nullptr;
+  float *d_tr = nullptr;
+  size_t tr_bytes = 0;
 };
 
 namespace {
@@ -1073,7 +1080,7 @@ void esc_context_destroy(esc_context *ctx) {
                   ctx->d_bvh_tri_blocks_p, ctx->d_bvh_sph_blocks_p,
                   ctx->d_tri_boxes, ctx->d_sph_boxes, ctx->d_bin_hdr, ctx->d_bin_tri_ids,
                   ctx->d_bin_sph_ids, ctx->lbins.face_hdr, ctx->lbins.counts, ctx->lbins.tri_ids,
-                  ctx->lbins.sph_ids, ctx->d_qstats, ctx->d_sstats, ctx->d_ss};
+                  ctx->lbins.sph_ids, ctx->d_qstats, ctx->d_sstats, ctx->d_ss, ctx->d_tstats, ctx->d_tr};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t ev : ctx->ev)
@@ -2230,12 +2237,10 @@ static int shade_stats_reset(esc_context *ctx) {
   return ESC_OK;
 }
 
-// k_shade_rays on n rays; the caller has validated everything and reset the stats
-static int shade_launch(esc_context *ctx, const char *fn, int64_t n, const float *d_origins, const float *d_dirs,
-                        uint32_t pixel_base, const esc_render_options *opts, uint64_t seed, float *d_rgb,
-                        uint8_t *d_rgb8, float *d_t, int32_t *d_geom, int32_t *d_prim) {
-  if (n == 0) return ESC_OK;
-  esc::ShadeParams p;
+// the parameter block of k_shade_rays / k_trace for n rays of an already validated call
+static void shade_params(esc_context *ctx, esc::ShadeParams &p, int64_t n, const float *d_origins,
+                         const float *d_dirs, uint32_t pixel_base, const esc_render_options *opts, uint64_t seed,
+                         float *d_rgb, uint8_t *d_rgb8) {
   std::memset(&p, 0, sizeof(p));
   p.q.n = n;
   p.q.orig = d_origins;
@@ -2244,9 +2249,6 @@ static int shade_launch(esc_context *ctx, const char *fn, int64_t n, const float
   p.q.exact_only = (opts->flags & ESC_RENDER_EXACT_ONLY) ? 1 : 0;
   p.rgb = d_rgb;
   p.rgb8 = d_rgb8;
-  p.t = d_t;
-  p.geom = d_geom;
-  p.prim = d_prim;
   p.tri_n = ctx->d_tri_n;
   p.mat = ctx->d_mat;
   p.sph_mat = ctx->d_sph_mat;
@@ -2258,6 +2260,18 @@ static int shade_launch(esc_context *ctx, const char *fn, int64_t n, const float
   p.fixed_face = opts->fixed_face;
   p.seed = seed;
   p.pixel_base = pixel_base;
+}
+
+// k_shade_rays on n rays; the caller has validated everything and reset the stats
+static int shade_launch(esc_context *ctx, const char *fn, int64_t n, const float *d_origins, const float *d_dirs,
+                        uint32_t pixel_base, const esc_render_options *opts, uint64_t seed, float *d_rgb,
+                        uint8_t *d_rgb8, float *d_t, int32_t *d_geom, int32_t *d_prim) {
+  if (n == 0) return ESC_OK;
+  esc::ShadeParams p;
+  shade_params(ctx, p, n, d_origins, d_dirs, pixel_base, opts, seed, d_rgb, d_rgb8);
+  p.t = d_t;
+  p.geom = d_geom;
+  p.prim = d_prim;
   p.stats = ctx->d_sstats;
   const int e = esc_launch_shade_rays(&p, ctx->stream);
   if (e) {
@@ -2378,44 +2392,54 @@ int esc_last_shade_stats(esc_context *ctx, esc_shade_stats *out) {
   return ESC_OK;
 }
 
-int esc_render_supersampled(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
-                            const esc_render_options *opts, float *d_image, uint8_t *d_u8) {
-  const char *fn = "esc_render_supersampled";
+// argument checks of the supersampled / traced frames; nn receives n of spp = n*n
+static int frame_args_ok(esc_context *ctx, const char *fn_, const esc_camera *cam, int32_t W, int32_t H,
+                         int32_t spp, const esc_render_options *opts, float *d_image, int &nn) {
+  const std::string fn(fn_);
   if (!ctx || !cam || !opts || !d_image) {
-    set_error(!ctx ? "esc_render_supersampled: ctx is null" : "esc_render_supersampled: bad argument");
+    set_error(!ctx ? fn + ": ctx is null" : fn + ": bad argument");
     return ESC_ERR_INVALID;
   }
-  int nn = 0;
+  nn = 0;
   for (int k = 1; k <= 8; ++k)
     if (k * k == spp) nn = k;
   if (!nn) {
-    set_error("esc_render_supersampled: spp must be n*n with n in 1..8");
+    set_error(fn + ": spp must be n*n with n in 1..8");
     return ESC_ERR_INVALID;
   }
   if (W < 2 || H < 2) {
-    set_error("esc_render_supersampled: need W,H >= 2");
+    set_error(fn + ": need W,H >= 2");
     return ESC_ERR_INVALID;
   }
   if ((int64_t)W * H > 0x7fffffffLL) {
-    set_error("esc_render_supersampled: W*H exceeds the reference's int pixel index (main.cpp:784)");
+    set_error(fn + ": W*H exceeds the reference's int pixel index (main.cpp:784)");
     return ESC_ERR_INVALID;
   }
   if (!ctx->have_scene) {
-    set_error("esc_render_supersampled: no scene uploaded");
+    set_error(fn + ": no scene uploaded");
     return ESC_ERR_INVALID;
   }
   for (int k = 0; k < 3; k++)
     if (!std::isfinite(cam->origin[k]) || !std::isfinite(cam->lower_left_corner[k]) ||
         !std::isfinite(cam->horizontal[k]) || !std::isfinite(cam->vertical[k])) {
-      set_error("esc_render_supersampled: camera is not finite");
+      set_error(fn + ": camera is not finite");
       return ESC_ERR_INVALID;
     }
-  int rc = shade_options_ok(ctx, fn, opts);
+  const int rc = shade_options_ok(ctx, fn_, opts);
   if (rc) return rc;
   if (((uintptr_t)d_image) & 3u) {
-    set_error("esc_render_supersampled: d_image must be 4-byte aligned");
+    set_error(fn + ": d_image must be 4-byte aligned");
     return ESC_ERR_INVALID;
   }
+  return ESC_OK;
+}
+
+int esc_render_supersampled(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
+                            const esc_render_options *opts, float *d_image, uint8_t *d_u8) {
+  const char *fn = "esc_render_supersampled";
+  int nn = 0;
+  int rc = frame_args_ok(ctx, fn, cam, W, H, spp, opts, d_image, nn);
+  if (rc) return rc;
   HIP_TRY(hipSetDevice(ctx->device));
   // bands of whole rows (of pixels when one row does not fit) within the scratch budget
   const int64_t total = (int64_t)W * H;
@@ -2440,6 +2464,186 @@ int esc_render_supersampled(esc_context *ctx, const esc_camera *cam, int32_t W, 
       if ((rc = camera_launch(ctx, fn, cam, W, H, p0, n, nullptr, dx, dy, d_o, d_d))) return rc;
       if ((rc = shade_launch(ctx, fn, n, d_o, d_d, (uint32_t)p0, opts, opts->seed + (uint64_t)k, d_rgb, nullptr,
                              nullptr, nullptr, nullptr)))
+        return rc;
+      const int e = esc_launch_ss_accumulate(img, d_rgb, 3 * n, k == 0 ? 1 : 0, ctx->stream);
+      if (e) {
+        set_error(std::string(fn) + ": k_ss_accumulate launch: " + hipGetErrorString((hipError_t)e));
+        return ESC_ERR_HIP;
+      }
+    }
+    const int e = esc_launch_ss_finish(img, d_u8 ? d_u8 + 3 * p0 : nullptr, 3 * n, (float)spp, ctx->stream);
+    if (e) {
+      set_error(std::string(fn) + ": k_ss_finish launch: " + hipGetErrorString((hipError_t)e));
+      return ESC_ERR_HIP;
+    }
+  }
+  return ESC_OK;
+}
+
+
+// ---- mirror reflections (rt_trace.hip) -------------------------------------------------------------
+constexpr int kTraceStats = 5 + esc::kTraceMaxDepth + 1;
+constexpr int kTraceCounters = esc::kTraceMaxDepth + 2; // uint32 queue counters, after the stats
+constexpr size_t kTraceQueueBytes = 2 * esc::kTraceQueuePlanes * sizeof(float); // both queues, per ray
+
+static int trace_args_ok(const char *fn, int32_t max_depth, float bias) {
+  if (max_depth < 0 || max_depth > ESC_TRACE_MAX_DEPTH) {
+    set_error(std::string(fn) + ": max_depth must be in 0..16");
+    return ESC_ERR_INVALID;
+  }
+  if (!(bias >= 0.f) || !std::isfinite(bias)) {
+    set_error(std::string(fn) + ": bias must be finite and >= 0");
+    return ESC_ERR_INVALID;
+  }
+  return ESC_OK;
+}
+
+static int trace_stats_reset(esc_context *ctx) {
+  const size_t bytes = kTraceStats * sizeof(unsigned long long) + kTraceCounters * sizeof(uint32_t);
+  if (!ctx->d_tstats) HIP_TRY(hipMalloc((void **)&ctx->d_tstats, bytes));
+  HIP_TRY(hipMemsetAsync(ctx->d_tstats, 0, kTraceStats * sizeof(unsigned long long), ctx->stream));
+  return ESC_OK;
+}
+
+// grow-only scratch of the bounce loop.  No recorded frame reads it, so no epoch is involved.
+static int trace_scratch(esc_context *ctx, size_t bytes) {
+  if (ctx->tr_bytes >= bytes) return ESC_OK;
+  if (ctx->d_tr) HIP_TRY(hipFree(ctx->d_tr));
+  ctx->d_tr = nullptr;
+  ctx->tr_bytes = 0;
+  HIP_TRY(hipMalloc((void **)&ctx->d_tr, bytes));
+  ctx->tr_bytes = bytes;
+  return ESC_OK;
+}
+
+// the bounce loop on one batch of n rays: levels 0 .. max_depth, one launch each, nothing waited for.
+// d_queues: 2 * kTraceQueuePlanes * n floats.  The caller has validated everything and reset the stats.
+static int trace_launch(esc_context *ctx, const char *fn, int64_t n, const float *d_origins, const float *d_dirs,
+                        uint32_t pixel_base, const esc_render_options *opts, uint64_t seed, int32_t max_depth,
+                        float bias, float *d_rgb, uint8_t *d_rgb8, float *d_queues) {
+  if (n == 0) return ESC_OK;
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(ctx->d_tstats + kTraceStats);
+  HIP_TRY(hipMemsetAsync(cnt, 0, kTraceCounters * sizeof(uint32_t), ctx->stream));
+  esc::TraceParams p;
+  std::memset(&p, 0, sizeof(p));
+  shade_params(ctx, p.s, n, d_origins, d_dirs, pixel_base, opts, seed, d_rgb, d_rgb8);
+  p.s.stats = ctx->d_tstats;
+  p.max_depth = max_depth;
+  p.bias = bias;
+  float *queue[2] = {d_queues, d_queues + (size_t)esc::kTraceQueuePlanes * (size_t)n};
+  for (int k = 0; k <= max_depth; ++k) {
+    p.level = k;
+    p.s.seed = seed + 64ull * (uint64_t)k;
+    p.q_in = queue[k & 1];
+    p.q_out = queue[(k + 1) & 1];
+    p.n_in = cnt + k; // counter k: the rays of level k, written by level k - 1
+    p.n_out = cnt + k + 1;
+    const int e = esc_launch_trace_level(&p, ctx->stream);
+    if (e) {
+      set_error(std::string(fn) + ": k_trace launch: " + hipGetErrorString((hipError_t)e));
+      return ESC_ERR_HIP;
+    }
+  }
+  return ESC_OK;
+}
+
+int esc_trace_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs, uint32_t pixel_base,
+                   const esc_render_options *opts, int32_t max_depth, float bias, float *d_rgb, uint8_t *d_rgb8) {
+  const char *fn = "esc_trace_rays";
+  if (!ctx || !opts) {
+    set_error(!ctx ? "esc_trace_rays: ctx is null" : "esc_trace_rays: opts is null");
+    return ESC_ERR_INVALID;
+  }
+  if (!ctx->have_scene) {
+    set_error("esc_trace_rays: no scene uploaded (esc_upload_scene / esc_upload_flat)");
+    return ESC_ERR_INVALID;
+  }
+  if (n < 0) {
+    set_error("esc_trace_rays: n < 0");
+    return ESC_ERR_INVALID;
+  }
+  int rc = shade_options_ok(ctx, fn, opts);
+  if (rc) return rc;
+  if ((rc = trace_args_ok(fn, max_depth, bias))) return rc;
+  if (n > 0 && (!d_origins || !d_dirs || !d_rgb)) {
+    set_error("esc_trace_rays: d_origins, d_dirs and d_rgb are required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_origins | (uintptr_t)d_dirs | (uintptr_t)d_rgb) & 3u) {
+    set_error("esc_trace_rays: device pointers must be 4-byte aligned (d_rgb8 excepted)");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error("esc_trace_rays: n exceeds one launch (2^32 - 1 workgroups of 256 rays)");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  if ((rc = trace_stats_reset(ctx))) return rc;
+  // batches of rays whose two queues fit the scratch budget (none is needed at depth 0)
+  const int64_t batch = max_depth == 0 ? n : std::min<int64_t>(n, (int64_t)(kSsScratchBytes / kTraceQueueBytes));
+  if (max_depth > 0 && (rc = trace_scratch(ctx, (size_t)batch * kTraceQueueBytes))) return rc;
+  for (int64_t r0 = 0; r0 < n; r0 += batch) {
+    const int64_t m = std::min(batch, n - r0);
+    if ((rc = trace_launch(ctx, fn, m, d_origins + 3 * r0, d_dirs + 3 * r0, pixel_base + (uint32_t)r0, opts,
+                           opts->seed, max_depth, bias, d_rgb + 3 * r0, d_rgb8 ? d_rgb8 + 3 * r0 : nullptr,
+                           ctx->d_tr)))
+      return rc;
+  }
+  return ESC_OK;
+}
+
+int esc_last_trace_stats(esc_context *ctx, esc_trace_stats *out) {
+  if (!ctx || !out) {
+    set_error(!ctx ? "esc_last_trace_stats: ctx is null" : "esc_last_trace_stats: out is null");
+    return ESC_ERR_INVALID;
+  }
+  unsigned long long h[kTraceStats] = {0};
+  if (ctx->d_tstats) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_tstats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  out->rays = 0; // the kernel keeps the rays per level only (rt_trace.hip)
+  out->hit_rays = h[1];
+  out->shadow_rays = h[2];
+  out->exact_rays = h[3];
+  out->exact_tests = h[4];
+  for (int k = 0; k <= ESC_TRACE_MAX_DEPTH; ++k) {
+    out->depth_rays[k] = h[5 + k];
+    out->rays += h[5 + k];
+  }
+  return ESC_OK;
+}
+
+int esc_render_traced(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
+                      int32_t max_depth, float bias, const esc_render_options *opts, float *d_image,
+                      uint8_t *d_u8) {
+  const char *fn = "esc_render_traced";
+  int nn = 0;
+  int rc = frame_args_ok(ctx, fn, cam, W, H, spp, opts, d_image, nn);
+  if (rc) return rc;
+  if ((rc = trace_args_ok(fn, max_depth, bias))) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  // bands of whole rows (of pixels when one row does not fit): origins, directions, colours and, past
+  // depth 0, both queues of a band within the scratch budget
+  const size_t per_ray = 9 * sizeof(float) + (max_depth > 0 ? kTraceQueueBytes : 0);
+  const int64_t total = (int64_t)W * H;
+  int64_t band = std::min<int64_t>(total, (int64_t)(kSsScratchBytes / per_ray));
+  if (band >= W) band -= band % W;
+  if ((rc = trace_scratch(ctx, (size_t)band * per_ray))) return rc;
+  float *d_o = ctx->d_tr, *d_d = d_o + 3 * (size_t)band, *d_rgb = d_o + 6 * (size_t)band;
+  float *d_queues = d_o + 9 * (size_t)band;
+  if ((rc = trace_stats_reset(ctx))) return rc;
+  for (int64_t p0 = 0; p0 < total; p0 += band) {
+    const int64_t n = std::min(band, total - p0);
+    float *img = d_image + 3 * p0;
+    for (int k = 0; k < spp; ++k) {
+      // esc_render_supersampled's sample k
+      const float dx = ((float)(k % nn) + 0.5f) / (float)nn - 0.5f;
+      const float dy = ((float)(k / nn) + 0.5f) / (float)nn - 0.5f;
+      if ((rc = camera_launch(ctx, fn, cam, W, H, p0, n, nullptr, dx, dy, d_o, d_d))) return rc;
+      if ((rc = trace_launch(ctx, fn, n, d_o, d_d, (uint32_t)p0, opts, opts->seed + (uint64_t)k, max_depth, bias,
+                             d_rgb, nullptr, d_queues)))
         return rc;
       const int e = esc_launch_ss_accumulate(img, d_rgb, 3 * n, k == 0 ? 1 : 0, ctx->stream);
       if (e) {

@@ -31,7 +31,11 @@
 //   --spp N       anti-aliased frame: N = n*n samples per pixel on a regular sub-pixel grid, n in 1..8
 //                 (esc_render_supersampled; one GPU, not with --ispc or --bvh).  The frame is the mean
 //                 of the samples; the PPM is written as usual
+//   --bounces N   mirror reflections: up to N (0..16) specular bounces weighted by the materials' ks
+//                 (esc_render_traced; combinable with --spp, otherwise under --spp's restrictions)
+//   --bias X      with --bounces: a bounce starts X (finite, >= 0; default 1e-4) off its surface
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -74,7 +78,9 @@ int main(int argc, char *argv[]) {
   int debug = 1; // INFO, debug.h:3
   float eye[3] = {0, 1, 3}, look[3] = {0, 1, 0}; // main.cpp:426
   int W = 1024, H = 768;                         // main.cpp:427
-  int gpus = 1, shadows = 1, fixed_face = -1, spp = 0;
+  int gpus = 1, shadows = 1, fixed_face = -1, spp = 0, bounces = -1;
+  float bias = 1e-4f;
+  bool have_bias = false;
   unsigned long long seed = 0;
 
   for (int arg = 1; arg < argc; arg++) {
@@ -120,12 +126,36 @@ int main(int argc, char *argv[]) {
       arg++;
       continue;
     }
+    if (a == "--bounces") {
+      if (!next) die("--bounces needs N");
+      char *end = nullptr;
+      const long v = std::strtol(next, &end, 10);
+      if (end == next || *end != '\0' || v < 0 || v > ESC_TRACE_MAX_DEPTH)
+        die(std::string("--bounces must be a whole number from 0 to 16, got ") + next);
+      bounces = (int)v;
+      arg++;
+      continue;
+    }
+    if (a == "--bias") {
+      if (!next) die("--bias needs X");
+      char *end = nullptr;
+      const float v = std::strtof(next, &end);
+      if (end == next || *end != '\0' || !(v >= 0.f) || !std::isfinite(v))
+        die(std::string("--bias must be a finite number >= 0, got ") + next);
+      bias = v;
+      have_bias = true;
+      arg++;
+      continue;
+    }
     if (a == "--dump-f32") { if (!next) die("--dump-f32 needs a path"); dumpname = next; arg++; continue; }
     die("Invalid Argument: " + a); // main.cpp:531-534
   }
   if (W < 2 || H < 2) die("window must be at least 2x2");
   if (gpus < 1) die("--gpus must be >= 1");
   if (spp && (ispc || flat || gpus != 1)) die("--spp renders on one GPU and not with --ispc, --bvh or --bvh-tree");
+  if (bounces >= 0 && (ispc || flat || gpus != 1))
+    die("--bounces renders on one GPU and not with --ispc, --bvh or --bvh-tree");
+  if (have_bias && bounces < 0) die("--bias needs --bounces");
 
   esc_scene *scene = esc_scene_new();
   if (!scene) die("out of memory");
@@ -210,13 +240,17 @@ int main(int argc, char *argv[]) {
                 << "\n num_light_faces = " << nlt << std::endl;
     trace(W, H, &icam, nt, tris, nl, lights, nlt, ltris, image.data(), debug, 0);
     esc_flat_free(fs);
-  } else if (ctx && spp) {
-    // device framebuffer of esc_render_supersampled, copied back like esc_render_frame_host's
+  } else if (ctx && (spp || bounces >= 0)) {
+    // device framebuffer of esc_render_supersampled / esc_render_traced, copied back like
+    // esc_render_frame_host's
     esc_render_options so = opts;
     so.flags = 0;
     float *d_image = nullptr;
     if (hipMalloc((void **)&d_image, image.size() * sizeof(float)) != hipSuccess) die("out of device memory");
-    check(esc_render_supersampled(ctx, &cam, W, H, spp, &so, d_image, nullptr), "render");
+    if (bounces >= 0)
+      check(esc_render_traced(ctx, &cam, W, H, spp ? spp : 1, bounces, bias, &so, d_image, nullptr), "render");
+    else
+      check(esc_render_supersampled(ctx, &cam, W, H, spp, &so, d_image, nullptr), "render");
     check(esc_context_synchronize(ctx), "render");
     if (hipMemcpy(image.data(), d_image, image.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
       die("copy back failed");

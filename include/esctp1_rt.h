@@ -560,6 +560,64 @@ int esc_last_shade_stats(esc_context *ctx, esc_shade_stats *out);
 int esc_render_supersampled(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
                             const esc_render_options *opts, float *d_image, uint8_t *d_u8);
 
+/* ---- mirror reflections: a fused on-device bounce loop (rt_trace.hip) ----
+ * An extension beyond the reference (which casts no secondary rays), driven by the material's ks.
+ * For one ray (o, d) with pixel id q = pixel_base + i (mod 2^32), max_depth = D and bias, all
+ * arithmetic fp32, one rounding per written operation, no contraction, vec.h's operation order for
+ * dot, normalize, vector +- and vector * scalar:
+ *
+ *   w = (1, 1, 1)
+ *   for k = 0 .. D:
+ *       (c, t0, id, N) = what esc_shade_rays computes for (o, d) with pixel id q and seed
+ *                        opts.seed + 64*k (mod 2^64): c the colour; t0 the closest-hit t of
+ *                        main.cpp:715-722 (NOT the t the light loop carries, quirk S3); N the shading
+ *                        normal of main.cpp:723-738 incl. quirk S1, spheres normalize((o + d*t0) - C)
+ *       C = c                       if k == 0
+ *       C = C + w * c               otherwise, per channel: fl(C + fl(w * c))
+ *       stop if id is a miss or k == D
+ *       w = w * ks(material of id)  per channel
+ *       stop unless (w.r > 0 || w.g > 0 || w.b > 0)      (a NaN or zero weight ends the path)
+ *       s  = dot(d, N)
+ *       Nf = (s > 0) ? -N : N
+ *       o' = (o + d * t0) + Nf * bias
+ *       d' = normalize(d - N * (2.f * s))
+ *       (o, d) = (o', d')
+ *   result C, and its PPM quantisation (main.cpp:676-682) in d_rgb8
+ *
+ * A supersampled frame's sample j at depth k uses seed + j + 64*k (j < 64).  A bounce ray is an
+ * ordinary ray to the sweeps: it passes the precondition gate of the queries or runs the reference
+ * loop in index order.  With bias == 0 a bounce may hit its own surface again at t ~ 0; that is
+ * defined behaviour (the reference's shadow rays have the same property) and bias is the remedy.
+ * max_depth == 0 is esc_shade_rays, bit for bit.
+ *
+ * Pointer, alignment, n == 0, flag and stage rules are esc_shade_rays'; ESC_RENDER_EXACT_ONLY sends
+ * every primary, bounce and shadow ray through the index-order loop.  max_depth outside 0..16 or a
+ * negative / NaN / infinite bias is ESC_ERR_INVALID.  Asynchronous on the context's stream: one
+ * launch per depth level, no host synchronisation between them; the ray queues live in scratch the
+ * context owns (rays are processed in batches so that it stays under 256 MB).  Like the queries the
+ * calls read only per-scene tables. */
+#define ESC_TRACE_MAX_DEPTH 16
+/* counts of the last esc_trace_rays / esc_render_traced call (a NEW struct: the others keep their
+ * layout).  rays counts every shaded ray, primary and bounce: the sum of depth_rays. */
+typedef struct esc_trace_stats {
+  uint64_t rays;
+  uint64_t hit_rays;
+  uint64_t shadow_rays;
+  uint64_t exact_rays;  /* primary, bounce and shadow rays that ran the index-order loop */
+  uint64_t exact_tests;
+  uint64_t depth_rays[ESC_TRACE_MAX_DEPTH + 1]; /* rays shaded at each level */
+} esc_trace_stats;
+int esc_trace_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs, uint32_t pixel_base,
+                   const esc_render_options *opts, int32_t max_depth, float bias, float *d_rgb, uint8_t *d_rgb8);
+/* camera rays -> the loop above -> the accumulate / finish of esc_render_supersampled (same spp
+ * rules, sample offsets and pixel ids), in row bands under the 256 MB scratch cap, queues included.
+ * max_depth == 0 is esc_render_supersampled, bit for bit. */
+int esc_render_traced(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
+                      int32_t max_depth, float bias, const esc_render_options *opts, float *d_image,
+                      uint8_t *d_u8);
+/* synchronises the context's stream */
+int esc_last_trace_stats(esc_context *ctx, esc_trace_stats *out);
+
 /* Whole frame into HOST memory, synchronous: render + D2H.  `image` = W*H*3 floats. */
 int esc_render_frame_host(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
                           const esc_render_options *opts, float *image, uint8_t *rgb8);
