@@ -15,13 +15,13 @@ from . import _capi
 from ._capi import (ESC_FACE_FIXED, ESC_FACE_HASH, ESC_STAGE_AUTO, ESC_STAGE_BVH, ESC_STAGE_LDS,
                     ESC_RENDER_EXACT_ONLY, ESC_RENDER_INDEX_ORDER, ESC_RENDER_SHADE_FUSED,
                     ESC_RENDER_SHADE_QUEUE, ESC_RENDER_TIME_KERNELS, ESC_RENDER_NO_TILE_LISTS, ESC_RENDER_NO_LIGHT_LISTS, ESC_RENDER_TWO_KERNELS, ESC_RENDER_BVH_HEURISTIC_PADS, ESC_RENDER_NO_COUNTERS,
-                    ESC_STAGE_SMEM, EscError,
+                    ESC_STAGE_SMEM, ESC_TRANSMIT_OFF, ESC_TRANSMIT_REFRACT, ESC_TRANSMIT_FRESNEL, EscError,
                     check)
 
 __all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "trace", "write_ppm", "quantise", "synthetic_view",
            "EscError", "ESC_FACE_FIXED", "ESC_FACE_HASH", "ESC_STAGE_AUTO", "ESC_STAGE_SMEM",
            "ESC_STAGE_LDS", "ESC_STAGE_BVH", "ESC_RENDER_EXACT_ONLY", "ESC_RENDER_TIME_KERNELS", "ESC_RENDER_INDEX_ORDER", "ESC_RENDER_SHADE_QUEUE",
-           "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "version"]
+           "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "ESC_TRANSMIT_OFF", "ESC_TRANSMIT_REFRACT", "ESC_TRANSMIT_FRESNEL", "version"]
 
 
 def _f32(a, shape=None):
@@ -33,6 +33,16 @@ def _f32(a, shape=None):
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+_TRANSMIT_MODES = {"off": ESC_TRANSMIT_OFF, "refract": ESC_TRANSMIT_REFRACT, "fresnel": ESC_TRANSMIT_FRESNEL}
+
+
+def _transmit_mode(transmission):
+    try:
+        return _TRANSMIT_MODES[transmission]
+    except (KeyError, TypeError):
+        raise ValueError(f"transmission must be 'off', 'refract' or 'fresnel', not {transmission!r}") from None
 
 
 def version():
@@ -121,6 +131,34 @@ class Scene:
         if n:
             check(self._lib.esc_scene_spheres_copy(self._h, _fp(s), _fp(m)))
         return s, m
+
+    # -- transmission (extension: the side table of esc_trace_rays_ex) -----------------
+    def set_transmission(self, geom, tf, ni):
+        """tf (3 floats, the MTL's Tf) and ni (its Ni) of geometry `geom`; tf = 0, ni = 1 is opaque."""
+        t = np.concatenate([_f32(tf, (3,)), _f32([ni], (1,))])
+        check(self._lib.esc_scene_set_geometry_transmission(self._h, int(geom), _fp(t)))
+
+    def set_sphere_transmission(self, first, tf, ni):
+        """tf (n x 3) and ni (n) of spheres first .. first + n - 1."""
+        tf = _f32(tf, (-1, 3))
+        ni = _f32(ni, (-1,))
+        if tf.shape[0] != ni.shape[0]:
+            raise ValueError("one ni per tf")
+        t = np.ascontiguousarray(np.concatenate([tf, ni[:, None]], axis=1))
+        check(self._lib.esc_scene_set_sphere_transmission(self._h, int(first), t.shape[0], _fp(t)))
+
+    def transmission(self, geom):
+        """(tf, ni) of geometry `geom`"""
+        t = np.zeros(4, np.float32)
+        check(self._lib.esc_scene_get_geometry_transmission(self._h, int(geom), _fp(t)))
+        return t[:3].copy(), t[3]
+
+    def sphere_transmission(self):
+        """(tf (n x 3), ni (n)) of the spheres"""
+        t = np.zeros((self.info()["n_spheres"], 4), np.float32)
+        if len(t):
+            check(self._lib.esc_scene_get_sphere_transmission(self._h, _fp(t)))
+        return t[:, :3].copy(), t[:, 3].copy()
 
     def build_accel(self, origin, which):
         """Host-side build of the ESC_STAGE_BVH tree (no GPU needed): which = 'triangles' |
@@ -560,22 +598,29 @@ class Renderer:
         return {k: getattr(s, k) for k in ("rays", "hit_rays", "shadow_rays", "exact_rays", "exact_tests")}
 
     def trace_rays(self, origins, dirs, rgb, *, max_depth, bias, rgb8=None, pixel_base=0, shadows=True,
-                   face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False):
+                   face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False, transmission="off"):
         """Mirror reflections (esc_trace_rays): shade_rays' colour plus up to max_depth (0..16) specular
         bounces weighted by the materials' ks; bias >= 0 moves a bounce's origin off its surface.
         Asynchronous on the renderer's stream, one launch per depth level.  Contiguous device tensors
-        as for shade_rays; max_depth=0 is shade_rays bit for bit."""
+        as for shade_rays; max_depth=0 is shade_rays bit for bit.  transmission="refract" | "fresnel"
+        (esc_trace_rays_ex): materials with a transmission entry refract; "off" is the plain call."""
         import torch
+        mode = _transmit_mode(transmission)
         n, po, pd, _ = self._query_inputs(origins, dirs, None)
         args = (self._query_ptr("rgb", rgb, torch.float32, (n, 3)),
                 None if rgb8 is None else self._query_ptr("rgb8", rgb8, torch.uint8, (n, 3)))
         o = _options(shadows, face_mode, fixed_face, seed, ESC_STAGE_AUTO, 0,
                      ESC_RENDER_EXACT_ONLY if exact else 0)
-        check(self._lib.esc_trace_rays(self._h, n, po, pd, int(pixel_base) & 0xffffffff, C.byref(o),
-                                       int(max_depth), float(bias), *args))
+        if mode == ESC_TRANSMIT_OFF:
+            check(self._lib.esc_trace_rays(self._h, n, po, pd, int(pixel_base) & 0xffffffff, C.byref(o),
+                                           int(max_depth), float(bias), *args))
+        else:
+            to = _capi.esc_trace_options(int(max_depth), float(bias), mode, 0)
+            check(self._lib.esc_trace_rays_ex(self._h, n, po, pd, int(pixel_base) & 0xffffffff, C.byref(o),
+                                              C.byref(to), *args))
 
     def trace(self, origins, dirs, *, max_depth, bias, pixel_base=0, shadows=True, face_mode=ESC_FACE_FIXED,
-              fixed_face=0, seed=0, exact=False):
+              fixed_face=0, seed=0, exact=False, transmission="off"):
         """Synchronous tracing of numpy rays: {"rgb", "rgb8"} as numpy arrays."""
         import torch
         to, td, _ = self._stage(origins, dirs, None)
@@ -583,15 +628,16 @@ class Renderer:
         rgb = torch.empty((n, 3), dtype=torch.float32, device=to.device)
         rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=to.device)
         self.trace_rays(to, td, rgb, max_depth=max_depth, bias=bias, rgb8=rgb8, pixel_base=pixel_base,
-                        shadows=shadows, face_mode=face_mode, fixed_face=fixed_face, seed=seed, exact=exact)
+                        shadows=shadows, face_mode=face_mode, fixed_face=fixed_face, seed=seed, exact=exact,
+                        transmission=transmission)
         self.synchronize()
         return {"rgb": rgb.cpu().numpy(), "rgb8": rgb8.cpu().numpy()}
 
     def render_traced(self, camera, W, H, *, spp=1, max_depth, bias, want_u8=False, shadows=True,
-                      face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False):
+                      face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False, transmission="off"):
         """Frame with mirror reflections (esc_render_traced): render_supersampled's samples, each
         traced through up to max_depth bounces.  Returns numpy fp32 (H, W, 3) and optionally the
-        quantised bytes.  Synchronous."""
+        quantised bytes.  Synchronous.  transmission as for trace_rays (esc_render_traced_ex)."""
         import torch
         dev = torch.device("cuda", self.device)
         img = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
@@ -599,9 +645,15 @@ class Renderer:
         o = _options(shadows, face_mode, fixed_face, seed, ESC_STAGE_AUTO, 0,
                      ESC_RENDER_EXACT_ONLY if exact else 0)
         torch.cuda.current_stream(dev).synchronize()  # the buffers were made on torch's stream
-        check(self._lib.esc_render_traced(self._h, C.byref(camera.c), W, H, int(spp), int(max_depth),
-                                          float(bias), C.byref(o), C.c_void_p(img.data_ptr()),
-                                          None if u8 is None else C.c_void_p(u8.data_ptr())))
+        mode = _transmit_mode(transmission)
+        out = (C.c_void_p(img.data_ptr()), None if u8 is None else C.c_void_p(u8.data_ptr()))
+        if mode == ESC_TRANSMIT_OFF:
+            check(self._lib.esc_render_traced(self._h, C.byref(camera.c), W, H, int(spp), int(max_depth),
+                                              float(bias), C.byref(o), *out))
+        else:
+            to = _capi.esc_trace_options(int(max_depth), float(bias), mode, 0)
+            check(self._lib.esc_render_traced_ex(self._h, C.byref(camera.c), W, H, int(spp), C.byref(o),
+                                                 C.byref(to), *out))
         self.synchronize()
         return (img.cpu().numpy(), u8.cpu().numpy()) if want_u8 else img.cpu().numpy()
 
@@ -614,6 +666,13 @@ class Renderer:
         out = {k: getattr(s, k) for k in ("rays", "hit_rays", "shadow_rays", "exact_rays", "exact_tests")}
         out["depth_rays"] = [int(v) for v in s.depth_rays]
         return out
+
+    def transmit_stats(self):
+        """Counts of the last trace_rays / render_traced call with a transmission mode: the rays sent on
+        as refracted, fresnel_reflected and total_internal (all zero after a plain call).  Synchronises."""
+        s = _capi.esc_transmit_stats()
+        check(self._lib.esc_last_transmit_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k in ("refracted", "fresnel_reflected", "total_internal")}
 
     def tile_lists(self, which):
         """the lists of the last frame (0 / 1: tile lists of spheres / triangles; 2 / 3: light lists of

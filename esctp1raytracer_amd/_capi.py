@@ -27,6 +27,10 @@ ESC_STAGE_SMEM = 1
 ESC_STAGE_LDS = 2
 ESC_STAGE_BVH = 3
 ESC_MATERIAL_FLOATS = 13
+ESC_TRANSMISSION_FLOATS = 4
+ESC_TRANSMIT_OFF = 0
+ESC_TRANSMIT_REFRACT = 1
+ESC_TRANSMIT_FRESNEL = 2
 ESC_RENDER_EXACT_ONLY = 1
 ESC_RENDER_TIME_KERNELS = 2
 ESC_RENDER_INDEX_ORDER = 4
@@ -99,6 +103,15 @@ class esc_trace_stats(C.Structure):
                 ("exact_rays", C.c_uint64), ("exact_tests", C.c_uint64), ("depth_rays", C.c_uint64 * 17)]
 
 
+class esc_trace_options(C.Structure):  # 16 bytes
+    _fields_ = [("max_depth", C.c_int32), ("bias", C.c_float), ("transmission", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class esc_transmit_stats(C.Structure):  # 24 bytes
+    _fields_ = [("refracted", C.c_uint64), ("fresnel_reflected", C.c_uint64), ("total_internal", C.c_uint64)]
+
+
 class esc_bvh_node(C.Structure):  # 64 bytes
     _fields_ = [("lo0", C.c_float * 3), ("hi0", C.c_float * 3), ("lo1", C.c_float * 3),
                 ("hi1", C.c_float * 3), ("child", C.c_int32 * 2), ("minkey", C.c_uint32 * 2)]
@@ -133,6 +146,10 @@ SIGNATURES = {
     "esc_scene_geometry_copy": (C.c_int, [_P, C.c_int32, _F, _F, _U32, _F]),
     "esc_scene_light_sources": (C.c_int, [_P, _I32]),
     "esc_scene_spheres_copy": (C.c_int, [_P, _F, _F]),
+    "esc_scene_set_geometry_transmission": (C.c_int, [_P, C.c_int32, _F]),
+    "esc_scene_get_geometry_transmission": (C.c_int, [_P, C.c_int32, _F]),
+    "esc_scene_set_sphere_transmission": (C.c_int, [_P, C.c_int32, C.c_int32, _F]),
+    "esc_scene_get_sphere_transmission": (C.c_int, [_P, _F]),
     "esc_camera_init": (None, [C.POINTER(esc_camera), _F, _F, _F, C.c_float, C.c_float]),
     "esc_flatten_ispc": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
     "esc_flat_free": (None, [_P]),
@@ -197,6 +214,11 @@ SIGNATURES = {
     "esc_render_traced": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_float, C.POINTER(esc_render_options), _P, _P]),
     "esc_last_trace_stats": (C.c_int, [_P, C.POINTER(esc_trace_stats)]),
+    "esc_trace_rays_ex": (C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, C.POINTER(esc_render_options),
+                                    C.POINTER(esc_trace_options), _P, _P]),
+    "esc_render_traced_ex": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(esc_render_options), C.POINTER(esc_trace_options), _P, _P]),
+    "esc_last_transmit_stats": (C.c_int, [_P, C.POINTER(esc_transmit_stats)]),
     "esc_render_frame_host": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
                                         C.POINTER(esc_render_options), _F, _U8]),
     "esc_render_frame_multi": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,

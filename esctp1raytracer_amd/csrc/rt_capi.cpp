@@ -170,6 +170,10 @@ struct esc_context {
   unsigned long long *d_tstats = nullptr;
   float *d_tr = nullptr;
   size_t tr_bytes = 0;
+  // transmission side table (tf[3], ni per material, indexed like d_mat) of esc_trace_rays_ex, and
+  // whether any of its entries is transmissive: only then do the TRANSMIT kernels run
+  float *d_transmit = nullptr;
+  bool any_transmissive = false;
 };
 
 namespace {
@@ -181,6 +185,7 @@ struct Staged {
   std::vector<esc::DevSph> sph;
   std::vector<int32_t> sph_mat;
   std::vector<esc::DevMat> mat;
+  std::vector<float> transmit; // 4 per entry of mat: tf[3], ni
   std::vector<esc::DevLight> lights;
   std::vector<float> light_points; // xyz0
   int n_geom = 0;
@@ -219,6 +224,11 @@ void push_light_point(Staged &s, const float *v) {
   s.light_points.push_back(0.0f);
 }
 
+void push_transmission(Staged &s, const esc::Transmission &t) {
+  s.transmit.insert(s.transmit.end(), t.tf, t.tf + 3);
+  s.transmit.push_back(t.ni);
+}
+
 int stage_scene(const esc_scene &scene, Staged &s) {
   bool any_normals = false;
   for (const auto &g : scene.geometry) any_normals |= !g.normals.empty();
@@ -227,6 +237,7 @@ int stage_scene(const esc_scene &scene, Staged &s) {
     const esc::Geometry &g = scene.geometry[gi];
     const bool hn = !g.normals.empty();
     s.mat.push_back(dev_material(g.object_material, hn));
+    push_transmission(s, g.transmission);
     for (size_t f = 0; f < g.n_faces(); f++) {
       const uint32_t *face = &g.face_index[3 * f];
       s.tri.push_back(dev_triangle(&g.vertex[3 * face[0]], &g.vertex[3 * face[1]],
@@ -254,6 +265,7 @@ int stage_scene(const esc_scene &scene, Staged &s) {
     s.sph.push_back(d);
     s.sph_mat.push_back(s.n_geom + (int)k);
     s.mat.push_back(dev_material(scene.sphere_materials[k], false));
+    push_transmission(s, k < scene.sphere_transmission.size() ? scene.sphere_transmission[k] : esc::Transmission());
   }
   for (size_t li : scene.light_sources) { // main.cpp:740-748
     const esc::Geometry &g = scene.geometry[li];
@@ -291,6 +303,7 @@ int stage_flat(int32_t nt, const ispc_triangle *tris, int32_t nl, const ispc_lig
   s.n_geom = max_geom + 1;
   s.mat.resize((size_t)s.n_geom);
   std::memset(s.mat.data(), 0, s.mat.size() * sizeof(esc::DevMat));
+  for (int g = 0; g < s.n_geom; g++) push_transmission(s, esc::Transmission()); // the seam carries none
   for (int i = 0; i < nt; i++) {
     const ispc_triangle &t = tris[i];
     s.tri.push_back(dev_triangle(t.vertices[0], t.vertices[1], t.vertices[2], t.geom_id));
@@ -869,6 +882,7 @@ int commit(esc_context *ctx, const Staged &s) {
   if ((rc = upload_vec(ctx->d_sph2, sph2, ctx->stream))) return rc;
   if ((rc = upload_vec(ctx->d_sph_mat, s.sph_mat, ctx->stream))) return rc;
   if ((rc = upload_vec(ctx->d_mat, s.mat, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->d_transmit, s.transmit, ctx->stream))) return rc;
   if ((rc = upload_vec(ctx->d_lights, s.lights, ctx->stream))) return rc;
   if ((rc = upload_vec(ctx->d_light_points, s.light_points, ctx->stream))) return rc;
   if ((rc = alloc_dev(ctx->d_tri_p, s.tri.size()))) return rc;
@@ -878,6 +892,11 @@ int commit(esc_context *ctx, const Staged &s) {
   ctx->n_sph = (int)s.sph.size();
   ctx->n_lights = (int)s.lights.size();
   ctx->n_geom = s.n_geom;
+  ctx->any_transmissive = false;
+  for (size_t i = 0; i + 3 < s.transmit.size(); i += 4) { // the kernel's test (rt_transmit.h)
+    const float *t = &s.transmit[i];
+    ctx->any_transmissive |= (t[0] > 0.f || t[1] > 0.f || t[2] > 0.f) && t[3] > 0.f;
+  }
   ctx->min_light_faces = 0;
   for (size_t i = 0; i < s.lights.size(); i++)
     ctx->min_light_faces = (i == 0) ? s.lights[i].n_faces
@@ -1080,7 +1099,8 @@ void esc_context_destroy(esc_context *ctx) {
                   ctx->d_bvh_tri_blocks_p, ctx->d_bvh_sph_blocks_p,
                   ctx->d_tri_boxes, ctx->d_sph_boxes, ctx->d_bin_hdr, ctx->d_bin_tri_ids,
                   ctx->d_bin_sph_ids, ctx->lbins.face_hdr, ctx->lbins.counts, ctx->lbins.tri_ids,
-                  ctx->lbins.sph_ids, ctx->d_qstats, ctx->d_sstats, ctx->d_ss, ctx->d_tstats, ctx->d_tr};
+                  ctx->lbins.sph_ids, ctx->d_qstats, ctx->d_sstats, ctx->d_ss, ctx->d_tstats, ctx->d_tr,
+                  ctx->d_transmit};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t ev : ctx->ev)
@@ -2482,7 +2502,7 @@ int esc_render_supersampled(esc_context *ctx, const esc_camera *cam, int32_t W, 
 
 
 // ---- mirror reflections (rt_trace.hip) -------------------------------------------------------------
-constexpr int kTraceStats = 5 + esc::kTraceMaxDepth + 1;
+constexpr int kTraceStatWords = esc::kTraceStats + esc::kTransmitStats; // esc_trace_stats, esc_transmit_stats
 constexpr int kTraceCounters = esc::kTraceMaxDepth + 2; // uint32 queue counters, after the stats
 constexpr size_t kTraceQueueBytes = 2 * esc::kTraceQueuePlanes * sizeof(float); // both queues, per ray
 
@@ -2499,9 +2519,9 @@ static int trace_args_ok(const char *fn, int32_t max_depth, float bias) {
 }
 
 static int trace_stats_reset(esc_context *ctx) {
-  const size_t bytes = kTraceStats * sizeof(unsigned long long) + kTraceCounters * sizeof(uint32_t);
+  const size_t bytes = kTraceStatWords * sizeof(unsigned long long) + kTraceCounters * sizeof(uint32_t);
   if (!ctx->d_tstats) HIP_TRY(hipMalloc((void **)&ctx->d_tstats, bytes));
-  HIP_TRY(hipMemsetAsync(ctx->d_tstats, 0, kTraceStats * sizeof(unsigned long long), ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->d_tstats, 0, kTraceStatWords * sizeof(unsigned long long), ctx->stream));
   return ESC_OK;
 }
 
@@ -2520,9 +2540,9 @@ static int trace_scratch(esc_context *ctx, size_t bytes) {
 // d_queues: 2 * kTraceQueuePlanes * n floats.  The caller has validated everything and reset the stats.
 static int trace_launch(esc_context *ctx, const char *fn, int64_t n, const float *d_origins, const float *d_dirs,
                         uint32_t pixel_base, const esc_render_options *opts, uint64_t seed, int32_t max_depth,
-                        float bias, float *d_rgb, uint8_t *d_rgb8, float *d_queues) {
+                        float bias, int32_t transmission, float *d_rgb, uint8_t *d_rgb8, float *d_queues) {
   if (n == 0) return ESC_OK;
-  uint32_t *cnt = reinterpret_cast<uint32_t *>(ctx->d_tstats + kTraceStats);
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(ctx->d_tstats + kTraceStatWords);
   HIP_TRY(hipMemsetAsync(cnt, 0, kTraceCounters * sizeof(uint32_t), ctx->stream));
   esc::TraceParams p;
   std::memset(&p, 0, sizeof(p));
@@ -2530,6 +2550,10 @@ static int trace_launch(esc_context *ctx, const char *fn, int64_t n, const float
   p.s.stats = ctx->d_tstats;
   p.max_depth = max_depth;
   p.bias = bias;
+  if (transmission != ESC_TRANSMIT_OFF && ctx->any_transmissive) { // else the mirror-only kernels
+    p.transmit = ctx->d_transmit;
+    p.transmit_mode = transmission;
+  }
   float *queue[2] = {d_queues, d_queues + (size_t)esc::kTraceQueuePlanes * (size_t)n};
   for (int k = 0; k <= max_depth; ++k) {
     p.level = k;
@@ -2547,34 +2571,44 @@ static int trace_launch(esc_context *ctx, const char *fn, int64_t n, const float
   return ESC_OK;
 }
 
-int esc_trace_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs, uint32_t pixel_base,
-                   const esc_render_options *opts, int32_t max_depth, float bias, float *d_rgb, uint8_t *d_rgb8) {
-  const char *fn = "esc_trace_rays";
-  if (!ctx || !opts) {
-    set_error(!ctx ? "esc_trace_rays: ctx is null" : "esc_trace_rays: opts is null");
+// the mode and the reserved word of esc_trace_options
+static int transmit_args_ok(const char *fn, const esc_trace_options *topts) {
+  if (topts->transmission < ESC_TRANSMIT_OFF || topts->transmission > ESC_TRANSMIT_FRESNEL) {
+    set_error(std::string(fn) + ": transmission must be ESC_TRANSMIT_OFF, _REFRACT or _FRESNEL");
     return ESC_ERR_INVALID;
   }
+  if (topts->reserved != 0) {
+    set_error(std::string(fn) + ": reserved must be 0");
+    return ESC_ERR_INVALID;
+  }
+  return ESC_OK;
+}
+
+static int trace_rays_impl(const char *fn_, esc_context *ctx, int64_t n, const float *d_origins,
+                           const float *d_dirs, uint32_t pixel_base, const esc_render_options *opts,
+                           int32_t max_depth, float bias, int32_t transmission, float *d_rgb, uint8_t *d_rgb8) {
+  const std::string fn(fn_);
   if (!ctx->have_scene) {
-    set_error("esc_trace_rays: no scene uploaded (esc_upload_scene / esc_upload_flat)");
+    set_error(fn + ": no scene uploaded (esc_upload_scene / esc_upload_flat)");
     return ESC_ERR_INVALID;
   }
   if (n < 0) {
-    set_error("esc_trace_rays: n < 0");
+    set_error(fn + ": n < 0");
     return ESC_ERR_INVALID;
   }
-  int rc = shade_options_ok(ctx, fn, opts);
+  int rc = shade_options_ok(ctx, fn_, opts);
   if (rc) return rc;
-  if ((rc = trace_args_ok(fn, max_depth, bias))) return rc;
+  if ((rc = trace_args_ok(fn_, max_depth, bias))) return rc;
   if (n > 0 && (!d_origins || !d_dirs || !d_rgb)) {
-    set_error("esc_trace_rays: d_origins, d_dirs and d_rgb are required");
+    set_error(fn + ": d_origins, d_dirs and d_rgb are required");
     return ESC_ERR_INVALID;
   }
   if (((uintptr_t)d_origins | (uintptr_t)d_dirs | (uintptr_t)d_rgb) & 3u) {
-    set_error("esc_trace_rays: device pointers must be 4-byte aligned (d_rgb8 excepted)");
+    set_error(fn + ": device pointers must be 4-byte aligned (d_rgb8 excepted)");
     return ESC_ERR_INVALID;
   }
   if (n > (int64_t)0xffffffffu * 256) {
-    set_error("esc_trace_rays: n exceeds one launch (2^32 - 1 workgroups of 256 rays)");
+    set_error(fn + ": n exceeds one launch (2^32 - 1 workgroups of 256 rays)");
     return ESC_ERR_INVALID;
   }
   HIP_TRY(hipSetDevice(ctx->device));
@@ -2584,11 +2618,53 @@ int esc_trace_rays(esc_context *ctx, int64_t n, const float *d_origins, const fl
   if (max_depth > 0 && (rc = trace_scratch(ctx, (size_t)batch * kTraceQueueBytes))) return rc;
   for (int64_t r0 = 0; r0 < n; r0 += batch) {
     const int64_t m = std::min(batch, n - r0);
-    if ((rc = trace_launch(ctx, fn, m, d_origins + 3 * r0, d_dirs + 3 * r0, pixel_base + (uint32_t)r0, opts,
-                           opts->seed, max_depth, bias, d_rgb + 3 * r0, d_rgb8 ? d_rgb8 + 3 * r0 : nullptr,
-                           ctx->d_tr)))
+    if ((rc = trace_launch(ctx, fn_, m, d_origins + 3 * r0, d_dirs + 3 * r0, pixel_base + (uint32_t)r0, opts,
+                           opts->seed, max_depth, bias, transmission, d_rgb + 3 * r0,
+                           d_rgb8 ? d_rgb8 + 3 * r0 : nullptr, ctx->d_tr)))
       return rc;
   }
+  return ESC_OK;
+}
+
+int esc_trace_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs, uint32_t pixel_base,
+                   const esc_render_options *opts, int32_t max_depth, float bias, float *d_rgb, uint8_t *d_rgb8) {
+  if (!ctx || !opts) {
+    set_error(!ctx ? "esc_trace_rays: ctx is null" : "esc_trace_rays: opts is null");
+    return ESC_ERR_INVALID;
+  }
+  return trace_rays_impl("esc_trace_rays", ctx, n, d_origins, d_dirs, pixel_base, opts, max_depth, bias,
+                         ESC_TRANSMIT_OFF, d_rgb, d_rgb8);
+}
+
+int esc_trace_rays_ex(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs,
+                      uint32_t pixel_base, const esc_render_options *opts, const esc_trace_options *topts,
+                      float *d_rgb, uint8_t *d_rgb8) {
+  const char *fn = "esc_trace_rays_ex";
+  if (!ctx || !opts || !topts) {
+    set_error(!ctx ? "esc_trace_rays_ex: ctx is null"
+                   : !opts ? "esc_trace_rays_ex: opts is null" : "esc_trace_rays_ex: trace options are null");
+    return ESC_ERR_INVALID;
+  }
+  const int rc = transmit_args_ok(fn, topts);
+  if (rc) return rc;
+  return trace_rays_impl(fn, ctx, n, d_origins, d_dirs, pixel_base, opts, topts->max_depth, topts->bias,
+                         topts->transmission, d_rgb, d_rgb8);
+}
+
+int esc_last_transmit_stats(esc_context *ctx, esc_transmit_stats *out) {
+  if (!ctx || !out) {
+    set_error(!ctx ? "esc_last_transmit_stats: ctx is null" : "esc_last_transmit_stats: out is null");
+    return ESC_ERR_INVALID;
+  }
+  unsigned long long h[esc::kTransmitStats] = {0};
+  if (ctx->d_tstats) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_tstats + esc::kTraceStats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  out->refracted = h[0];
+  out->fresnel_reflected = h[1];
+  out->total_internal = h[2];
   return ESC_OK;
 }
 
@@ -2597,7 +2673,7 @@ int esc_last_trace_stats(esc_context *ctx, esc_trace_stats *out) {
     set_error(!ctx ? "esc_last_trace_stats: ctx is null" : "esc_last_trace_stats: out is null");
     return ESC_ERR_INVALID;
   }
-  unsigned long long h[kTraceStats] = {0};
+  unsigned long long h[esc::kTraceStats] = {0};
   if (ctx->d_tstats) {
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemcpyAsync(h, ctx->d_tstats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
@@ -2615,10 +2691,9 @@ int esc_last_trace_stats(esc_context *ctx, esc_trace_stats *out) {
   return ESC_OK;
 }
 
-int esc_render_traced(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
-                      int32_t max_depth, float bias, const esc_render_options *opts, float *d_image,
-                      uint8_t *d_u8) {
-  const char *fn = "esc_render_traced";
+static int render_traced_impl(const char *fn, esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
+                              int32_t spp, int32_t max_depth, float bias, int32_t transmission,
+                              const esc_render_options *opts, float *d_image, uint8_t *d_u8) {
   int nn = 0;
   int rc = frame_args_ok(ctx, fn, cam, W, H, spp, opts, d_image, nn);
   if (rc) return rc;
@@ -2643,7 +2718,7 @@ int esc_render_traced(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
       const float dy = ((float)(k / nn) + 0.5f) / (float)nn - 0.5f;
       if ((rc = camera_launch(ctx, fn, cam, W, H, p0, n, nullptr, dx, dy, d_o, d_d))) return rc;
       if ((rc = trace_launch(ctx, fn, n, d_o, d_d, (uint32_t)p0, opts, opts->seed + (uint64_t)k, max_depth, bias,
-                             d_rgb, nullptr, d_queues)))
+                             transmission, d_rgb, nullptr, d_queues)))
         return rc;
       const int e = esc_launch_ss_accumulate(img, d_rgb, 3 * n, k == 0 ? 1 : 0, ctx->stream);
       if (e) {
@@ -2658,6 +2733,27 @@ int esc_render_traced(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
     }
   }
   return ESC_OK;
+}
+
+int esc_render_traced(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
+                      int32_t max_depth, float bias, const esc_render_options *opts, float *d_image,
+                      uint8_t *d_u8) {
+  return render_traced_impl("esc_render_traced", ctx, cam, W, H, spp, max_depth, bias, ESC_TRANSMIT_OFF, opts,
+                            d_image, d_u8);
+}
+
+int esc_render_traced_ex(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
+                         const esc_render_options *opts, const esc_trace_options *topts, float *d_image,
+                         uint8_t *d_u8) {
+  const char *fn = "esc_render_traced_ex";
+  if (!ctx || !topts) {
+    set_error(!ctx ? "esc_render_traced_ex: ctx is null" : "esc_render_traced_ex: trace options are null");
+    return ESC_ERR_INVALID;
+  }
+  const int rc = transmit_args_ok(fn, topts);
+  if (rc) return rc;
+  return render_traced_impl(fn, ctx, cam, W, H, spp, topts->max_depth, topts->bias, topts->transmission, opts,
+                            d_image, d_u8);
 }
 
 int esc_reset_counters(esc_context *ctx) {

@@ -1,6 +1,6 @@
-// rt_trace.hip -- Whitted-style mirror reflection on top of scan_row's body: one launch per depth
-// level, one ray per lane, no host synchronisation between the levels (the
-// definition is in include/esctp1_rt.h at esc_trace_rays).
+// rt_trace.hip -- Whitted-style mirror reflection and refraction on top of scan_row's body: one launch
+// per depth level, one ray per lane, no host synchronisation between the levels (DESIGN.md §3.13 and
+// §3.14; the definitions are in include/esctp1_rt.h at esc_trace_rays and esc_trace_options).
 //
 //   level k   reads its rays (k == 0: the caller's arrays, weight 1, destination = the ray's index;
 //             k >= 1: queue k & 1, whose live count is read from device memory, lanes past it
@@ -21,12 +21,15 @@
 
 #include "rt_shade_body.h"
 #include "rt_trace.h"
+#include "rt_transmit.h"
 
 namespace esc {
 
 // FIRST: level 0 (the caller's arrays).  LAST: level max_depth, which never bounces: without the bounce
 // nothing of the ray outlives the light loop, and the kernel is k_shade_rays plus the update of C.
-template <bool FIRST, bool LAST>
+// TRANSMIT: the scene has a transmissive material and the call asked for refraction (rt_transmit.h);
+// every other call runs the <*, *, false> instantiations, which are the mirror-only kernels unchanged.
+template <bool FIRST, bool LAST, bool TRANSMIT>
 __global__ __launch_bounds__(256) void k_trace(const TraceParams T) {
   const ShadeParams &P = T.s;
   const QueryParams &p = P.q;
@@ -81,9 +84,24 @@ __global__ __launch_bounds__(256) void k_trace(const TraceParams T) {
   }
 
   // ---- the bounce
+  uint32_t what = kBounceMirror; // TRANSMIT: what a transmissive hit did (rt_transmit.h)
   if (!LAST) {
     bool go = has_hit;
-    if (go) {
+    f3 o2 = mk(0.f, 0.f, 0.f), d2 = mk(0.f, 0.f, 0.f);
+    bool glass = false;
+    if constexpr (TRANSMIT) {
+      if (go) {
+        const float *tr = T.transmit + kTransmitFloats * (int64_t)mi;
+        const f3 tf = mk(tr[0], tr[1], tr[2]);
+        const float ni = tr[3];
+        glass = transmissive(tf.x, tf.y, tf.z, ni);
+        if (glass)
+          what = transmit_bounce(T.transmit_mode, P.seed, P.pixel_base + dest, tf, ni, T.bias, o, d, s.t, N, w,
+                                 o2, d2, go);
+        if (!go) what = kBounceMirror; // a refracted ray without weight is not counted
+      }
+    }
+    if (go && !glass) {
       w = mk(w.x * P.mat[mi].ks[0], w.y * P.mat[mi].ks[1], w.z * P.mat[mi].ks[2]);
       go = w.x > 0.f || w.y > 0.f || w.z > 0.f; // a NaN or zero weight ends the path
     }
@@ -96,10 +114,12 @@ __global__ __launch_bounds__(256) void k_trace(const TraceParams T) {
       base = (uint32_t)__shfl((int)base, 0, 64);
       const int64_t slot = (int64_t)base + lane;
       if (go && slot < cap) {
-        const float sn = dot(d, N);
-        const f3 Nf = (sn > 0.f) ? mk(-N.x, -N.y, -N.z) : N;
-        const f3 o2 = (o + d * s.t) + Nf * T.bias;
-        const f3 d2 = normalize(d - N * (2.f * sn));
+        if (!glass) {
+          const float sn = dot(d, N);
+          const f3 Nf = (sn > 0.f) ? mk(-N.x, -N.y, -N.z) : N;
+          o2 = (o + d * s.t) + Nf * T.bias;
+          d2 = normalize(d - N * (2.f * sn));
+        }
         float *q = T.q_out + slot;
         q[0] = o2.x;
         q[cap] = o2.y;
@@ -131,6 +151,16 @@ __global__ __launch_bounds__(256) void k_trace(const TraceParams T) {
     if (exact) atomicAdd(&P.stats[3], exact);
     if (tests) atomicAdd(&P.stats[4], tests);
   }
+  if constexpr (TRANSMIT && !LAST) { // esc_transmit_stats, the same way
+    const unsigned long long n1 = __popcll(__builtin_amdgcn_ballot_w64(what == kBounceRefracted));
+    const unsigned long long n2 = __popcll(__builtin_amdgcn_ballot_w64(what == kBounceFresnel));
+    const unsigned long long n3 = __popcll(__builtin_amdgcn_ballot_w64(what == kBounceTotalInternal));
+    if ((threadIdx.x & 63) == 0) {
+      if (n1) atomicAdd(&P.stats[kTraceStats + 0], n1);
+      if (n2) atomicAdd(&P.stats[kTraceStats + 1], n2);
+      if (n3) atomicAdd(&P.stats[kTraceStats + 2], n3);
+    }
+  }
 }
 
 } // namespace esc
@@ -139,13 +169,19 @@ extern "C" int esc_launch_trace_level(const esc::TraceParams *p, hipStream_t str
   if (p->s.q.n <= 0) return 0;
   const dim3 grid((unsigned)((p->s.q.n + 255) / 256));
   const bool first = p->level == 0, last = p->level == p->max_depth;
+  // a last level never bounces: <*, true, true> would be <*, true, false>
+  const bool transmit = p->transmit != nullptr && p->transmit_mode != esc::kTransmitOff && !last;
   if (first && last)
-    hipLaunchKernelGGL((esc::k_trace<true, true>), grid, dim3(256), 0, stream, *p);
-  else if (first)
-    hipLaunchKernelGGL((esc::k_trace<true, false>), grid, dim3(256), 0, stream, *p);
+    hipLaunchKernelGGL((esc::k_trace<true, true, false>), grid, dim3(256), 0, stream, *p);
   else if (last)
-    hipLaunchKernelGGL((esc::k_trace<false, true>), grid, dim3(256), 0, stream, *p);
+    hipLaunchKernelGGL((esc::k_trace<false, true, false>), grid, dim3(256), 0, stream, *p);
+  else if (first && transmit)
+    hipLaunchKernelGGL((esc::k_trace<true, false, true>), grid, dim3(256), 0, stream, *p);
+  else if (first)
+    hipLaunchKernelGGL((esc::k_trace<true, false, false>), grid, dim3(256), 0, stream, *p);
+  else if (transmit)
+    hipLaunchKernelGGL((esc::k_trace<false, false, true>), grid, dim3(256), 0, stream, *p);
   else
-    hipLaunchKernelGGL((esc::k_trace<false, false>), grid, dim3(256), 0, stream, *p);
+    hipLaunchKernelGGL((esc::k_trace<false, false, false>), grid, dim3(256), 0, stream, *p);
   return (int)hipGetLastError();
 }

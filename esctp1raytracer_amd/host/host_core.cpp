@@ -218,6 +218,70 @@ int esc_scene_spheres_copy(const esc_scene *scene, float *spheres_xyzr, float *m
   return ESC_OK;
 }
 
+// ----------------------------------------------------------- transmission
+int esc_scene_set_geometry_transmission(esc_scene *scene, int32_t geom, const float tr[ESC_TRANSMISSION_FLOATS]) {
+  if (!scene || !tr) {
+    set_error("esc_scene_set_geometry_transmission: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  if (geom < 0 || (size_t)geom >= scene->geometry.size()) {
+    set_error("esc_scene_set_geometry_transmission: geom out of range");
+    return ESC_ERR_INVALID;
+  }
+  esc::Transmission &t = scene->geometry[geom].transmission;
+  std::memcpy(t.tf, tr, 12);
+  std::memcpy(&t.ni, tr + 3, 4);
+  return ESC_OK;
+}
+
+int esc_scene_get_geometry_transmission(const esc_scene *scene, int32_t geom, float tr[ESC_TRANSMISSION_FLOATS]) {
+  if (!scene || !tr) {
+    set_error("esc_scene_get_geometry_transmission: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  if (geom < 0 || (size_t)geom >= scene->geometry.size()) {
+    set_error("esc_scene_get_geometry_transmission: geom out of range");
+    return ESC_ERR_INVALID;
+  }
+  const esc::Transmission &t = scene->geometry[geom].transmission;
+  std::memcpy(tr, t.tf, 12);
+  std::memcpy(tr + 3, &t.ni, 4);
+  return ESC_OK;
+}
+
+int esc_scene_set_sphere_transmission(esc_scene *scene, int32_t first, int32_t n, const float *tr) {
+  if (!scene || n < 0 || (n > 0 && !tr)) {
+    set_error("esc_scene_set_sphere_transmission: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  if (first < 0 || (int64_t)first + n > (int64_t)scene->spheres.size()) {
+    set_error("esc_scene_set_sphere_transmission: first .. first + n out of range");
+    return ESC_ERR_INVALID;
+  }
+  if (n > 0 && scene->sphere_transmission.size() < scene->spheres.size())
+    scene->sphere_transmission.resize(scene->spheres.size());
+  for (int32_t i = 0; i < n; i++) {
+    esc::Transmission &t = scene->sphere_transmission[(size_t)first + i];
+    std::memcpy(t.tf, tr + (size_t)i * ESC_TRANSMISSION_FLOATS, 12);
+    std::memcpy(&t.ni, tr + (size_t)i * ESC_TRANSMISSION_FLOATS + 3, 4);
+  }
+  return ESC_OK;
+}
+
+int esc_scene_get_sphere_transmission(const esc_scene *scene, float *tr) {
+  if (!scene || (!tr && !scene->spheres.empty())) {
+    set_error("esc_scene_get_sphere_transmission: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  for (size_t i = 0; i < scene->spheres.size(); i++) {
+    const esc::Transmission t =
+        i < scene->sphere_transmission.size() ? scene->sphere_transmission[i] : esc::Transmission();
+    std::memcpy(tr + i * ESC_TRANSMISSION_FLOATS, t.tf, 12);
+    std::memcpy(tr + i * ESC_TRANSMISSION_FLOATS + 3, &t.ni, 4);
+  }
+  return ESC_OK;
+}
+
 // ----------------------------------------------------------------- camera
 // camera.h:16-29, evaluated exactly as written there
 void esc_camera_init(esc_camera *cam, const float lookfrom[3], const float lookat[3],

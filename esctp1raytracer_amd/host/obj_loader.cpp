@@ -141,6 +141,10 @@ bool next_line(std::istream &in, std::string &line) {
 struct MtlEntry {
   std::string name;
   Material m;
+  // tinyobj's transmittance / ior / illum defaults; they reach the scene as a Transmission (load_obj)
+  float tf[3] = {0, 0, 0};
+  float ni = 1.f;
+  int illum = 0;
 };
 
 // returns false + message on anything tinyobj would report as a warning
@@ -201,7 +205,18 @@ bool read_mtl(const std::string &path, std::vector<MtlEntry> &mats, std::map<std
       has_tr = true;
       continue;
     }
-    // everything else (Ni, illum, Tf, map_*, PBR terms) does not reach the renderer
+    if (t[0] == 'T' && t[1] == 'f' && is_blank(t[2])) { rgb(cur.tf); continue; }
+    if (t[0] == 'N' && t[1] == 'i' && is_blank(t[2])) {
+      c.p = t + 2;
+      cur.ni = c.number();
+      continue;
+    }
+    if (keyword(t, "illum")) {
+      c.p = t + 6;
+      cur.illum = (int)c.number();
+      continue;
+    }
+    // everything else (map_*, PBR terms) does not reach the renderer
   }
   flush(); // the last (or the unnamed default) material is always appended
   return true;
@@ -378,6 +393,15 @@ int load_obj(esc_scene &scene, const std::string &path) {
       float m13[ESC_MATERIAL_FLOATS];
       material_to_floats(g.object_material, m13);
       material_from_floats(m13, g.object_material); // sets lightsource, :63-64
+    }
+    {
+      // the MTL illumination models with transparency or refraction (4, 6, 7, 9) make Tf / Ni count;
+      // under any other model the material is opaque whatever its Tf says
+      const MtlEntry &me = materials[(size_t)mid];
+      if (me.illum == 4 || me.illum == 6 || me.illum == 7 || me.illum == 9) {
+        std::memcpy(g.transmission.tf, me.tf, 12);
+        g.transmission.ni = me.ni;
+      }
     }
     const size_t nf = sh.corners.size() / 3;
     for (size_t f = 0; f < nf; f++) {

@@ -23,11 +23,19 @@ struct Material { // scene.h:11-18
   bool lightsource = false;
 };
 
+// Transmission of a material (extension, esc_trace_rays_ex): the MTL's Tf and Ni.  A side record, not
+// part of Material: the 13-float material keeps its layout everywhere.  The default is opaque.
+struct Transmission {
+  float tf[3] = {0, 0, 0};
+  float ni = 1.f;
+};
+
 struct Geometry {               // scene.h:20-31
   std::vector<float> vertex;    // xyz per vertex
   std::vector<float> normals;   // xyz per vertex, may be empty or shorter (sceneloader.cpp:84-89)
   std::vector<uint32_t> face_index; // 3 per face
   Material object_material;
+  Transmission transmission;
   std::string name;
   size_t n_vertices() const { return vertex.size() / 3; }
   size_t n_normals() const { return normals.size() / 3; }
@@ -46,6 +54,8 @@ struct esc_scene {
   std::vector<size_t> light_sources;        // scene.h:35
   std::vector<esc::Sphere> spheres;         // extension
   std::vector<esc::Material> sphere_materials; // one per sphere
+  // one per sphere once any was set; shorter (or empty) means opaque for the rest
+  std::vector<esc::Transmission> sphere_transmission;
   size_t n_triangles() const {
     size_t n = 0;
     for (const auto &g : geometry) n += g.n_faces();

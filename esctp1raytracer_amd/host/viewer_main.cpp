@@ -34,6 +34,11 @@
 //   --bounces N   mirror reflections: up to N (0..16) specular bounces weighted by the materials' ks
 //                 (esc_render_traced; combinable with --spp, otherwise under --spp's restrictions)
 //   --bias X      with --bounces: a bounce starts X (finite, >= 0; default 1e-4) off its surface
+//   --refract     with --bounces: materials with a transmission entry (MTL Tf / Ni under illum 4, 6, 7, 9)
+//                 refract; total internal reflection reflects (esc_render_traced_ex, ESC_TRANSMIT_REFRACT)
+//   --fresnel     with --bounces: the same, and Schlick's term picks reflection or refraction per
+//                 sample by a hash (ESC_TRANSMIT_FRESNEL; use it with --spp).  Not with --refract
+//   --help        print the options and leave
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -70,6 +75,19 @@ void parse_floats(const char *flag, char *arg, float *out, int n, const char *er
   if (i != n) die(err);
 }
 
+const char *kUsage =
+    "ESCViewer2021 [-m model.obj | --scene c2|c3|c4|c5[:n]] [-o out.ppm] [-v x,y,z] [-l x,y,z] [-w W,H]\n"
+    "  --thread --bvh --bvh-tree --ispc --ispc-sorted --test --debug --trace   the reference's modes\n"
+    "  --gpus N [--rccl]          strips over N bands\n"
+    "  --shadows 0|1 --seed S --face K   shadow rays, light-face choice\n"
+    "  --dump-f32 path            raw fp32 framebuffer\n"
+    "  --spp N                    N = n*n samples per pixel, n in 1..8\n"
+    "  --bounces N                up to N (0..16) bounces: mirror reflections weighted by ks\n"
+    "  --bias X                   with --bounces: a bounce starts X off its surface (default 1e-4)\n"
+    "  --refract                  with --bounces: transmissive materials (Tf / Ni) refract\n"
+    "  --fresnel                  with --bounces: Schlick's term picks reflection or refraction per sample\n"
+    "  --help                     this text\n";
+
 } // namespace
 
 int main(int argc, char *argv[]) {
@@ -80,7 +98,7 @@ int main(int argc, char *argv[]) {
   int W = 1024, H = 768;                         // main.cpp:427
   int gpus = 1, shadows = 1, fixed_face = -1, spp = 0, bounces = -1;
   float bias = 1e-4f;
-  bool have_bias = false;
+  bool have_bias = false, refract = false, fresnel = false;
   unsigned long long seed = 0;
 
   for (int arg = 1; arg < argc; arg++) {
@@ -147,6 +165,12 @@ int main(int argc, char *argv[]) {
       arg++;
       continue;
     }
+    if (a == "--refract") { refract = true; continue; }
+    if (a == "--fresnel") { fresnel = true; continue; }
+    if (a == "--help") {
+      std::cout << kUsage;
+      return 0;
+    }
     if (a == "--dump-f32") { if (!next) die("--dump-f32 needs a path"); dumpname = next; arg++; continue; }
     die("Invalid Argument: " + a); // main.cpp:531-534
   }
@@ -156,6 +180,9 @@ int main(int argc, char *argv[]) {
   if (bounces >= 0 && (ispc || flat || gpus != 1))
     die("--bounces renders on one GPU and not with --ispc, --bvh or --bvh-tree");
   if (have_bias && bounces < 0) die("--bias needs --bounces");
+  if (refract && fresnel) die("--refract and --fresnel exclude each other");
+  if (refract && bounces < 0) die("--refract needs --bounces");
+  if (fresnel && bounces < 0) die("--fresnel needs --bounces");
 
   esc_scene *scene = esc_scene_new();
   if (!scene) die("out of memory");
@@ -247,7 +274,10 @@ int main(int argc, char *argv[]) {
     so.flags = 0;
     float *d_image = nullptr;
     if (hipMalloc((void **)&d_image, image.size() * sizeof(float)) != hipSuccess) die("out of device memory");
-    if (bounces >= 0)
+    if (bounces >= 0 && (refract || fresnel)) {
+      const esc_trace_options to = {bounces, bias, refract ? ESC_TRANSMIT_REFRACT : ESC_TRANSMIT_FRESNEL, 0};
+      check(esc_render_traced_ex(ctx, &cam, W, H, spp ? spp : 1, &so, &to, d_image, nullptr), "render");
+    } else if (bounces >= 0)
       check(esc_render_traced(ctx, &cam, W, H, spp ? spp : 1, bounces, bias, &so, d_image, nullptr), "render");
     else
       check(esc_render_supersampled(ctx, &cam, W, H, spp, &so, d_image, nullptr), "render");

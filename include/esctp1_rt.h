@@ -95,6 +95,21 @@ int esc_scene_geometry_copy(const esc_scene *scene, int32_t geom, float *vertex,
 int esc_scene_light_sources(const esc_scene *scene, int32_t *geom_ids /* [n_lights] */);
 int esc_scene_spheres_copy(const esc_scene *scene, float *spheres_xyzr, float *materials);
 
+/* EXTENSION: transmission of a material, for esc_trace_rays_ex / esc_render_traced_ex.  A side table
+ * next to the 13-float material (whose layout does not change): tf[3], the transmission filter
+ * (MTL `Tf`), and ni, the index of refraction (MTL `Ni`).  The default is tf = 0, ni = 1: opaque.
+ * Any float value is accepted, NaN included; the bounce rule at esc_trace_options says what it does.
+ * esc_scene_load_obj sets tf = Tf, ni = Ni on a geometry iff its material's `illum` is 4, 6, 7 or 9
+ * (the MTL illumination models with transparency or refraction); under any other model the geometry
+ * stays opaque whatever its Tf.  An index out of range is ESC_ERR_INVALID. */
+#define ESC_TRANSMISSION_FLOATS 4 /* tf[3], ni */
+int esc_scene_set_geometry_transmission(esc_scene *scene, int32_t geom, const float tr[ESC_TRANSMISSION_FLOATS]);
+int esc_scene_get_geometry_transmission(const esc_scene *scene, int32_t geom, float tr[ESC_TRANSMISSION_FLOATS]);
+/* spheres first .. first + n - 1; tr: n x 4 */
+int esc_scene_set_sphere_transmission(esc_scene *scene, int32_t first, int32_t n, const float *tr);
+/* tr: n_spheres x 4 */
+int esc_scene_get_sphere_transmission(const esc_scene *scene, float *tr);
+
 /* ------------------------------------------------------------------------------------
  * Camera == tracer::camera (src/scene/camera.h:7-41); ctor arithmetic runs on the host
  * ---------------------------------------------------------------------------------- */
@@ -617,6 +632,70 @@ int esc_render_traced(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
                       uint8_t *d_u8);
 /* synchronises the context's stream */
 int esc_last_trace_stats(esc_context *ctx, esc_trace_stats *out);
+
+/* ---- refraction: transmitted rays through glass and water (rt_trace.hip, rt_transmit.h, DESIGN.md
+ * section 3.14) ----
+ * The loop of esc_trace_rays with one more way of computing the next ray at a hit whose material has
+ * a transmission entry (esc_scene_set_geometry_transmission, esc_upload_scene; esc_upload_flat
+ * carries none: all opaque).  One ray per hit: a transmissive surface either refracts or reflects, so
+ * the queue bound and the plain update of C hold as before.  With T = (tf, ni) the table entry of the
+ * hit's material, q the ray's pixel id and seed_k the level's seed (opts.seed (+ j) + 64*k), the step
+ * after "stop if id is a miss or k == D" reads, with the same arithmetic rules as above:
+ *
+ *   transmissive = mode != OFF && (tf.r > 0 || tf.g > 0 || tf.b > 0) && ni > 0        (NaN: false)
+ *   if !transmissive:   the rule of esc_trace_rays (w = w * ks, stop unless some w > 0, mirror bounce)
+ *   else:
+ *       s   = dot(d, N);   Nf = (s > 0) ? -N : N;   c1 = (s > 0) ? s : -s
+ *       eta = (s > 0) ? ni : 1.f / ni                      (s > 0: the ray leaves the medium)
+ *       k   = 1.f - (eta * eta) * (1.f - c1 * c1)
+ *       reflect = !(k >= 0)                      (total internal reflection; also a NaN k)  -> total_internal
+ *       if !reflect && mode == FRESNEL:
+ *           r0 = (ni - 1.f) / (ni + 1.f);  r0 = r0 * r0
+ *           cx = (s > 0) ? sqrt(k) : c1                    (the cosine on the outside of the surface)
+ *           m  = 1.f - cx;   m2 = m * m;   F = r0 + (1.f - r0) * ((m2 * m2) * m)
+ *           u  = float(mix(seed_k, q, 0xFFFFFFFF) >> 8) * 2^-24
+ *           reflect = u < F                                                           -> fresnel_reflected
+ *       if reflect:   o' = (o + d * t0) + Nf * bias;   d' = normalize(d - N * (2.f * s))     (w unchanged)
+ *       else:         w = w * tf;  stop unless (w.r > 0 || w.g > 0 || w.b > 0)              -> refracted
+ *                     o' = (o + d * t0) - Nf * bias;   d' = normalize(d * eta + Nf * (eta * c1 - sqrt(k)))
+ *
+ * mix(seed, pixel, light) is the 64-bit mixer of the light-face hash (splitmix64's finaliser over
+ * seed + (pixel << 32 | light) + 0x9E3779B97F4A7C15), its high 32 bits before the modulo; no light has
+ * index 0xFFFFFFFF, so the choice is independent of the light-face choice.  The material's own colour
+ * c is still added at the hit; the ks of a transmissive material drives no bounce.  The medium
+ * outside every surface has index 1 (no nested media).  SHADOW RAYS ARE UNCHANGED: a transmissive
+ * primitive occludes like any other (the reference's occlusion loop).  With FRESNEL the two branches
+ * mix over the samples of esc_render_traced_ex (sample j has its own seed); REFRACT is the noise-free
+ * choice at spp 1.  esc_transmit_stats counts the rays each arrow above sent on to the next level
+ * (a refracted ray whose weight ends the path is not counted), so that with the mirror bounces they
+ * add up to depth_rays of the following levels.
+ *
+ * ESC_TRANSMIT_OFF is esc_trace_rays / esc_render_traced, bit for bit, and so is any mode on a scene
+ * without a transmissive entry.  transmission outside 0..2 or reserved != 0 is ESC_ERR_INVALID; the
+ * other argument rules are esc_trace_rays'.  esc_last_trace_stats works after these calls too. */
+#define ESC_TRANSMIT_OFF 0     /* esc_trace_rays, bit for bit */
+#define ESC_TRANSMIT_REFRACT 1 /* a transmissive surface refracts; total internal reflection reflects */
+#define ESC_TRANSMIT_FRESNEL 2 /* Schlick's F decides, by a hash of (seed, pixel, level), between the two */
+typedef struct esc_trace_options {
+  int32_t max_depth;
+  float bias;
+  int32_t transmission; /* ESC_TRANSMIT_* */
+  int32_t reserved;     /* 0 */
+} esc_trace_options;
+int esc_trace_rays_ex(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs,
+                      uint32_t pixel_base, const esc_render_options *opts, const esc_trace_options *trace_opts,
+                      float *d_rgb, uint8_t *d_rgb8);
+int esc_render_traced_ex(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
+                         const esc_render_options *opts, const esc_trace_options *trace_opts, float *d_image,
+                         uint8_t *d_u8);
+/* counts of the last esc_trace_rays_ex / esc_render_traced_ex call (zero after the plain forms) */
+typedef struct esc_transmit_stats {
+  uint64_t refracted;
+  uint64_t fresnel_reflected;
+  uint64_t total_internal;
+} esc_transmit_stats;
+/* synchronises the context's stream, like esc_last_trace_stats */
+int esc_last_transmit_stats(esc_context *ctx, esc_transmit_stats *out);
 
 /* Whole frame into HOST memory, synchronous: render + D2H.  `image` = W*H*3 floats. */
 int esc_render_frame_host(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
