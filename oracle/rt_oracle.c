@@ -233,6 +233,85 @@ uint32_t orc_face_hash(uint64_t seed, uint32_t pixel, uint32_t light, uint32_t n
   return (uint32_t)((z >> 32) % (uint64_t)n_faces);
 }
 
+/* ------------------------------------------------------ replaceable pow */
+
+/* One process-wide setting, written only between renders (orc_pow_set_mode / orc_pow_set_table)
+ * and read by the render threads; pthread_create / pthread_join order the two.  The miss counter
+ * is the only word the render threads write. */
+static int32_t pow_mode = ORC_POW_LIBM;
+static int32_t pow_steps = 0;
+static const uint64_t *pow_keys = NULL;
+static const float *pow_vals = NULL;
+static int64_t pow_n = 0;
+static uint64_t pow_misses = 0;
+
+int orc_pow_set_mode(int32_t mode, int32_t steps) {
+  if (mode < ORC_POW_LIBM || mode > ORC_POW_ROUNDED) return -1;
+  if (mode == ORC_POW_ROUNDED && (steps < -4 || steps > 4)) return -1;
+  pow_mode = mode;
+  pow_steps = mode == ORC_POW_ROUNDED ? steps : 0;
+  return 0;
+}
+
+int32_t orc_pow_get_mode(void) { return pow_mode; }
+
+int orc_pow_set_table(const uint64_t *keys, const float *values, int64_t n) {
+  if (n < 0 || (n > 0 && (!keys || !values))) return -1;
+  for (int64_t i = 1; i < n; i++)
+    if (keys[i - 1] >= keys[i]) return -1;
+  pow_keys = n > 0 ? keys : NULL;
+  pow_vals = n > 0 ? values : NULL;
+  pow_n = n > 0 ? n : 0;
+  return 0;
+}
+
+uint64_t orc_pow_misses(void) { return __atomic_load_n(&pow_misses, __ATOMIC_RELAXED); }
+void orc_pow_reset_misses(void) { __atomic_store_n(&pow_misses, 0, __ATOMIC_RELAXED); }
+
+static uint32_t f32_bits(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  return u;
+}
+
+/* main.cpp:783 pow(dot(N, H), Ns) */
+float orc_pow(float x, float Ns) {
+  switch (pow_mode) {
+  case ORC_POW_BASE:
+    return x;
+  case ORC_POW_EXPONENT:
+    return Ns;
+  case ORC_POW_ONE:
+    return 1.0f;
+  case ORC_POW_TABLE: {
+    const uint64_t key = ((uint64_t)f32_bits(x) << 32) | (uint64_t)f32_bits(Ns);
+    int64_t lo = 0, hi = pow_n;
+    while (lo < hi) {
+      const int64_t mid = lo + (hi - lo) / 2;
+      if (pow_keys[mid] < key)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    if (lo < pow_n && pow_keys[lo] == key) return pow_vals[lo];
+    __atomic_fetch_add(&pow_misses, 1, __ATOMIC_RELAXED);
+    return powf(x, Ns);
+  }
+  case ORC_POW_ROUNDED: {
+    float r = (float)pow((double)x, (double)Ns);
+    if (isnan(r) || isinf(r) || r == 0.f) return r;
+    const float to = pow_steps < 0 ? -INFINITY : INFINITY;
+    for (int32_t i = 0; i < abs(pow_steps); i++) {
+      r = nextafterf(r, to);
+      if (isinf(r) || r == 0.f) break; /* the end of the range: no further */
+    }
+    return r;
+  }
+  default:
+    return powf(x, Ns);
+  }
+}
+
 /* ---------------------------------------------------------------- scan_row */
 
 /* main.cpp:698-791, triangle branch (num_triangles == 0) */
@@ -336,7 +415,7 @@ static void scan_row(const orc_scene *s, const orc_camera *cam, int32_t W, int32
       orc_normalize(tmp, Hh); /* :780 */
 
       /* :782-783 c + (kd*d + ks*pow(dot(N,H), Ns)) / float(nl) */
-      float spec = powf(orc_dot(N, Hh), mat->Ns);
+      float spec = orc_pow(orc_dot(N, Hh), mat->Ns);
       float kd_d[3], ks_p[3];
       v_scale(mat->kd, d, kd_d);
       v_scale(mat->ks, spec, ks_p);

@@ -129,6 +129,32 @@ int orc_intersect_sphere(const float orig[3], const float dir[3], const float sp
 /* counter-based light-face choice shared with the HIP path (ORC_FACE_HASH) */
 uint32_t orc_face_hash(uint64_t seed, uint32_t pixel, uint32_t light, uint32_t n_faces);
 
+/* ---- the power of main.cpp:783, replaceable ----
+ * pow(dot(N, H), Ns) is the one term whose last bit the C library decides.  One process-wide
+ * setting selects what scan_row uses for it, so that tests can read the base and the exponent
+ * of every lit pixel out of a frame, feed another library's values back in, or bracket it.
+ * Set it only between renders; the render threads only read it (and count table misses).
+ * Every copy of rt_oracle.c (liboracle.so, liboracle_fast.so) has its own setting. */
+enum {
+  ORC_POW_LIBM = 0,     /* powf(x, Ns): the default, the reference's behaviour */
+  ORC_POW_BASE = 1,     /* x */
+  ORC_POW_EXPONENT = 2, /* Ns */
+  ORC_POW_ONE = 3,      /* 1.0f */
+  ORC_POW_TABLE = 4,    /* the value listed for (bits of x, bits of Ns); a miss is counted and
+                           answered with powf */
+  ORC_POW_ROUNDED = 5   /* (float)pow((double)x, (double)Ns) moved `steps` fp32 values up (> 0) or
+                           down (< 0) with nextafterf; NaN, inf and 0 results are left alone */
+};
+/* steps: -4..4, read for ORC_POW_ROUNDED only.  Returns 0, or -1 for a bad argument. */
+int orc_pow_set_mode(int32_t mode, int32_t steps);
+int32_t orc_pow_get_mode(void);
+/* keys[i] = (bits of x << 32) | bits of Ns, strictly increasing; the arrays stay the caller's
+ * and must outlive every render in ORC_POW_TABLE.  n = 0 clears.  -1 for n < 0, a null array or unsorted keys. */
+int orc_pow_set_table(const uint64_t *keys, const float *values, int64_t n);
+uint64_t orc_pow_misses(void);
+void orc_pow_reset_misses(void);
+float orc_pow(float x, float Ns);
+
 /* ---- frame ----
  * image: W*H*3 floats, pixel (w,h) at (h*W+w)*3, h = 0 is the bottom row
  * (main.cpp:784-786, flat layout of main.cpp:667-673).  Rows [row_begin,row_end)

@@ -316,7 +316,7 @@ static void scan_row8(const orc_scene *s, const orc_camera *cam, int32_t W, int3
         for (int k = 0; k < 3; k++) c[k] = (m->ka[k] * 0.5f + m->ke[k]) / nl; /* :769-770 */
         for (int k = 0; k < 3; k++) tmp[k] = (N[l][k] + L[l][k]) * 2.f;
         orc_normalize(tmp, Hh); /* :780 */
-        const float spec = powf(dot3(N[l], Hh), m->Ns);
+        const float spec = orc_pow(dot3(N[l], Hh), m->Ns); /* rt_oracle.c: the pow setting */
         for (int k = 0; k < 3; k++) c[k] = c[k] + (m->kd[k] * d + m->ks[k] * spec) / nl; /* :782-783 */
         px[l][0] += c[0]; /* :786-788 */
         px[l][1] += c[1];

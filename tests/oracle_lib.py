@@ -3,6 +3,7 @@ built in the authoring container, to the reference's own code (oracle/_ref/libre
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
 """
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -17,6 +18,8 @@ REF_SO = os.path.join(ORACLE_DIR, "_ref", "libref_pieces.so")
 
 ORC_FACE_FIXED, ORC_FACE_HASH = 0, 1
 ORC_QUIRK_S1, ORC_QUIRK_S3, ORC_QUIRK_ALL = 1, 2, 3
+# rt_oracle.h: what scan_row uses for pow(dot(N, H), Ns)
+POW_LIBM, POW_BASE, POW_EXPONENT, POW_ONE, POW_TABLE, POW_ROUNDED = range(6)
 
 _F = C.POINTER(C.c_float)
 
@@ -63,6 +66,18 @@ def build_oracle():
     subprocess.run(["make", "-C", ORACLE_DIR], check=True, stdout=subprocess.DEVNULL)
 
 
+def _declare_pow(lib):
+    lib.orc_pow_set_mode.restype = C.c_int
+    lib.orc_pow_set_mode.argtypes = [C.c_int32, C.c_int32]
+    lib.orc_pow_get_mode.restype = C.c_int32
+    lib.orc_pow_set_table.restype = C.c_int
+    lib.orc_pow_set_table.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.c_int64]
+    lib.orc_pow_misses.restype = C.c_uint64
+    lib.orc_pow_reset_misses.restype = None
+    lib.orc_pow.restype = C.c_float
+    lib.orc_pow.argtypes = [C.c_float, C.c_float]
+
+
 def oracle():
     global _oracle
     if _oracle is None:
@@ -93,6 +108,7 @@ def oracle():
         lib.orc_quantise.argtypes = [_F, C.c_int64, C.POINTER(C.c_uint8)]
         lib.orc_write_ppm.restype = C.c_int
         lib.orc_write_ppm.argtypes = [C.c_char_p, _F, C.c_int32, C.c_int32]
+        _declare_pow(lib)
         _oracle = lib
     return _oracle
 
@@ -122,8 +138,71 @@ def oracle_fast():
             C.POINTER(orc_scene), C.POINTER(orc_camera), C.c_int32, C.c_int32,
             C.POINTER(C.c_int32), C.c_int32, C.POINTER(orc_options), _F, C.POINTER(orc_counters),
             C.c_int32]
+        _declare_pow(lib)
         _oracle_fast = lib
     return _oracle_fast
+
+
+# --------------------------------------------------------------------------------------
+# the replaceable pow of main.cpp:783 (rt_oracle.h ORC_POW_*)
+# --------------------------------------------------------------------------------------
+def pow_key(x, ns):
+    """(bits of x << 32) | bits of Ns, as ORC_POW_TABLE looks a pair up"""
+    xb = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    nb = np.ascontiguousarray(ns, np.float32).view(np.uint32).astype(np.uint64)
+    return (xb << np.uint64(32)) | nb
+
+
+def pow_table(x, ns, values):
+    """sorted, duplicate-free (keys, values) for pow_mode(POW_TABLE, table=...).  Two different
+    values listed for one (x, Ns) are refused: a power is a function of its arguments."""
+    keys = pow_key(np.ravel(x), np.ravel(ns))
+    vals = np.ascontiguousarray(np.ravel(values), np.float32)
+    order = np.argsort(keys, kind="stable")
+    keys, vals = keys[order], vals[order]
+    first = np.ones(len(keys), bool)
+    first[1:] = keys[1:] != keys[:-1]
+    same = (vals[1:].view(np.uint32) == vals[:-1].view(np.uint32)) | first[1:]
+    assert same.all(), "one (x, Ns) pair with two different powers"
+    return np.ascontiguousarray(keys[first]), np.ascontiguousarray(vals[first])
+
+
+def _pow_libs():
+    """every loaded copy of rt_oracle.c has a setting of its own (liboracle_fast.so links one)"""
+    return [lib for lib in (oracle(), oracle_fast()) if lib is not None]
+
+
+def pow_misses():
+    """ORC_POW_TABLE lookups answered with powf since the last pow_mode() began"""
+    return sum(int(lib.orc_pow_misses()) for lib in _pow_libs())
+
+
+@contextlib.contextmanager
+def pow_mode(mode, steps=0, table=None):
+    """with pow_mode(POW_BASE): ...   every oracle render inside uses that power, both the scalar
+    and the packet library; the default (POW_LIBM) is restored on the way out, whatever happens.
+    table: (keys, values) of pow_table() for POW_TABLE.  Not re-entrant, and no render may be in
+    flight while it is entered or left."""
+    libs = _pow_libs()
+    assert all(lib.orc_pow_get_mode() == POW_LIBM for lib in libs), "pow_mode does not nest"
+    if mode == POW_TABLE:
+        keys, vals = table
+        assert keys.dtype == np.uint64 and vals.dtype == np.float32 and len(keys) == len(vals)
+    else:
+        assert table is None
+    try:
+        for lib in libs:
+            lib.orc_pow_reset_misses()
+            if mode == POW_TABLE:
+                rc = lib.orc_pow_set_table(keys.ctypes.data_as(C.POINTER(C.c_uint64)), fp(vals),
+                                           len(keys))
+                assert rc == 0, "table keys must be strictly increasing"
+            assert lib.orc_pow_set_mode(mode, steps) == 0, (mode, steps)
+        yield
+    finally:
+        for lib in libs:
+            lib.orc_pow_set_mode(POW_LIBM, 0)
+            lib.orc_pow_set_table(None, None, 0)
 
 
 def have_ref():
