@@ -7,12 +7,15 @@ of a lit pixel is (0 * 0.5 + 0) + (0 * d + 1 * sp) = sp exactly, and black other
 the scene is the renderer's power per lit pixel, bit for bit.  A light needs a ke to be a light: its
 probe material has ke = (1, 0, 0), so that its own lit pixels are (1 + sp, sp, sp).  The power is read
 from the green channel everywhere; blue must equal it, and red must be it or fl(1 + it)."""
-import contextlib
 import copy
+import functools
 
 import numpy as np
 
 import oracle_lib as ol
+import random_scenes as rs
+import ray_cases as rc
+import ray_oracle as ro
 
 F32 = np.float32
 NS_VALUES = (0.0, 1.0, 2.0, 16.5, 64.0, 120.0, 1000.0, 1024.0)
@@ -181,7 +184,6 @@ def probe_case(name):
         return (probe_split(ol.scene_from_product(sc), 0), tuple(float(v) for v in eye),
                 tuple(float(v) for v in look), 128, 72, 60.0, {})
     if name == "random":
-        import random_scenes as rs
         d, eye, look, W, H, vfov = rs.random_scene(RANDOM_SEED)
         return probe_split(d, 0), eye, look, W, H, vfov, {}
     raise KeyError(name)
@@ -302,17 +304,16 @@ _EDGE_RAYS = {}
 
 
 def edge_trace_rays():
-    """-> (the cornell edge scene, origins, targets): rays of a 16 x 12 frame and rays aimed at the mirror strip for which the
-    hand-built camera of test_trace_rays.py reproduces every bounce direction (chosen by the oracle)"""
+    """-> (the cornell edge scene, origins, targets): rays of a 16 x 12 frame and rays aimed at the mirror strip
+    for which the hand-built camera of ray_oracle.py reproduces every bounce direction (chosen by the oracle)"""
     if not _EDGE_RAYS:
-        import test_trace_rays as tt
         d, eye, look, _, _, _ = edge_scene("cornell")
-        o, a = tt.camera_targets(eye, look, 16, 12)
+        o, a = rc.camera_targets(eye, look, 16, 12)
         rng = np.random.default_rng(4)  # and 160 rays from around the eye to points on the mirror strip
         strip = np.stack([rng.uniform(-0.9, 0.9, 160), np.full(160, 0.015), rng.uniform(0.44, 0.66, 160)], 1)
         o = np.concatenate([o, np.array(eye, F32) + rng.uniform(-0.3, 0.3, (160, 3))]).astype(F32)
         a = np.concatenate([a, strip]).astype(F32)
-        keep = tt.oracle_trace(d, o, a, 2, float(F32(1e-4)))[2]
+        keep = ro.oracle_trace(d, o, a, 2, float(F32(1e-4)))["usable"]
         _EDGE_RAYS["v"] = (d, o[keep], a[keep])
     return _EDGE_RAYS["v"]
 
@@ -346,53 +347,25 @@ def oracle_with_table(d, eye, look, W, H, table, **kw):
 
 
 # ---- 3b: traced rays, a table gathered level by level ---------------------------------------------------
-def ray_colours(d, origins, llc, fixed_face=0, shadows=True):
-    """test_trace_rays.py::oracle_colours with `horizontal` = 0: the 2 x 2 frame's row 0 has a second
-    pixel, and with a zero `horizontal` it is the same ray as pixel (0, 0), whose colour is unchanged
-    (llc + (1, 0, 0) * 0 and llc + 0 * 0 are the same sum).  So every power the oracle takes inside is
-    one of the ray that is compared, and the table's miss counter speaks of those rays alone."""
-    import ctypes as C
-    lib = ol.oracle()
-    osc = ol.OracleScene(d)
-    opts = ol.orc_options(1 if shadows else 0, ol.ORC_FACE_FIXED, fixed_face, 0, ol.ORC_QUIRK_ALL)
-    n = origins.shape[0]
-    dirs, rgb = np.zeros((n, 3), F32), np.zeros((n, 3), F32)
-    img, out, cnt = np.zeros((2, 2, 3), F32), np.zeros(3, F32), ol.orc_counters()
-    for i in range(n):
-        cam = ol.orc_camera()
-        for k in range(3):
-            cam.origin[k] = float(origins[i, k])
-            cam.lower_left_corner[k] = float(llc[i, k])
-            cam.horizontal[k] = 0.0
-            cam.vertical[k] = (0.0, 1.0, 0.0)[k]
-        lib.orc_camera_get_ray(C.byref(cam), C.c_float(0), C.c_float(0), ol.fp(out))
-        dirs[i] = out
-        img[:] = 0
-        lib.orc_render(C.byref(osc.c), C.byref(cam), 2, 2, 0, 1, C.byref(opts), ol.fp(img), C.byref(cnt), 1)
-        assert np.array_equal(img[0, 0].view(np.uint32), img[0, 1].view(np.uint32)) or np.isnan(img[0]).any()
-        rgb[i] = img[0, 0]
-    return dirs, rgb
+# ray_oracle.ray_colours with `horizontal` = 0: every power the oracle takes inside is one of the ray that
+# is compared, so that the table's miss counter speaks of those rays alone
+ray_colours = functools.partial(ro.ray_colours, horizontal=(0, 0, 0))
 
 
-@contextlib.contextmanager
-def recorded_levels(module):
-    """inside, module.oracle_trace (test_trace_rays.py, test_transmission.py) takes each level's colours
-    from ray_colours, and every such call is recorded as (origins, targets, fixed_face, shadows, dirs)"""
-    calls, orig = [], module.oracle_colours
+def recorded_levels():
+    """-> (calls, colours): with oracle_trace(..., colours=colours) each level's colours come from
+    ray_colours, and every such call is recorded in `calls` as (origins, targets, fixed_face, shadows, dirs)"""
+    calls = []
 
-    def recording(d, origins, llc, fixed_face=0, shadows=True):
+    def colours(d, origins, llc, fixed_face=0, shadows=True):
         dirs, rgb = ray_colours(d, origins, llc, fixed_face, shadows)
         calls.append((origins.copy(), llc.copy(), fixed_face, shadows, dirs.copy()))
         return dirs, rgb
-    module.oracle_colours = recording
-    try:
-        yield calls
-    finally:
-        module.oracle_colours = orig
+    return calls, colours
 
 
 def table_from_levels(d, levels, shade_probe):
-    """levels: what recorded_levels() gathered while the restatement traced d (the rays of a level do not
+    """levels: the calls recorded_levels() gathered while the restatement traced d (the rays of a level do not
     depend on any power).  shade_probe(probe scene, origins, targets, dirs, fixed_face, shadows) -> (n, 3) colours
     from the renderer under test.  -> (keys, values) over every lit ray of every level"""
     probe = probe_keep_ns(d)
@@ -406,27 +379,25 @@ def table_from_levels(d, levels, shade_probe):
 
 
 def trace_ns_case(name):
-    """the `_ns` cases of test_trace_rays.py, all three with one light (CornellBox-Original; random_scene
+    """the `_ns` cases of ray_cases.py, all three with one light (CornellBox-Original; random_scene
     3 and 9: 1 + (seed % 7 == 0) + (seed % 11 == 0) lights)"""
-    import test_trace_rays as tt
-    d, o, a = tt.case_rays(name)
+    d, o, a = rc.trace_case_rays(name)
     assert name.endswith("_ns") and len(d["light_sources"]) == 1
     return d, o, a
 
 
-REFRACTION_SETTING = (3, float(F32(1e-4)), True)  # test_transmission.py's first: depth, bias, shadows
+REFRACTION_SETTING = (3, float(F32(1e-4)), True)  # TRANSMISSION_SETTINGS' first: depth, bias, shadows
 _REFRACTION = {}
 
 
 def refraction_ns_case(name="slab"):
-    """test_transmission.py's scene and camera, but specular all over: that module's walls have ks = 0
+    """a transmission case's scene and camera, but specular all over: the case's walls have ks = 0
     (no power reaches a colour there), so every surface that is not a light gets ks in [0.2, 0.6] unless
     it has one, and a random Ns in [1, 60]; the light keeps its loaded Ns.  The rays are then chosen as
-    that module chooses its own: those whose every bounce direction the hand-built camera reproduces, in
+    ray_cases.py chooses its own: those whose every bounce direction the hand-built camera reproduces, in
     both modes.  -> (scene, origins, targets)"""
     if name not in _REFRACTION:
-        import test_transmission as tx
-        d, o, a = tx._case(name)
+        d, o, a = rc.transmission_case(name)
         loaded = ol.load_dump("CornellBox-Original")
         rng = np.random.default_rng(6)
         for gi, g in enumerate(d["geometry"]):
@@ -440,8 +411,8 @@ def refraction_ns_case(name="slab"):
         assert len(d["light_sources"]) == 1 and all(g["material"][12] != 0 for g in d["geometry"])
         depth, bias, shadows = REFRACTION_SETTING
         keep = np.ones(len(o), bool)
-        for mode in (tx.REFRACT, tx.FRESNEL):
-            keep &= tx.oracle_trace(d, o, a, depth, bias, mode, shadows)["usable"]
+        for mode in (ro.REFRACT, ro.FRESNEL):
+            keep &= ro.oracle_trace(d, o, a, depth, bias, mode, shadows=shadows)["usable"]
         _REFRACTION[name] = (d, o[keep], a[keep])
     return _REFRACTION[name]
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+from model_files import models  # noqa: F401  (the fixture that unpacks cornell_models.tar.gz)
 
 ROOT = ol.ROOT
 
@@ -19,20 +20,6 @@ ROOT = ol.ROOT
 def esc():
     import esctp1raytracer_amd as m
     return m
-
-
-@pytest.fixture(scope="module")
-def models(tmp_path_factory):
-    """the reference's bundled models (cornell_box.obj and cornell/*.obj + .mtl, CC BY 3.0: see
-    cornell/copyright.txt), stored as tests/golden/cornell_models.tar.gz and unpacked per run"""
-    import tarfile
-    d = tmp_path_factory.mktemp("models")
-    with tarfile.open(os.path.join(ROOT, "tests", "golden", "cornell_models.tar.gz")) as t:
-        if hasattr(tarfile, "data_filter"):
-            t.extractall(d, filter="data")
-        else:
-            t.extractall(d)
-    return str(d)
 
 
 def test_library_exports_every_declared_symbol(esc):

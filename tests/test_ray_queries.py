@@ -3,7 +3,7 @@ reference arithmetic.
 
 The reference is the closest-hit / occlusion loop of main.cpp:176-192, 314-329 with the sphere
 extension (oracle closest_hit / occlusion order: triangles geometry by geometry and face by face,
-then spheres), written here over a numpy restatement of orc_intersect_triangle /
+then spheres) of tests/ray_oracle.py, over its numpy restatement of orc_intersect_triangle /
 orc_intersect_sphere.  test_numpy_restatement_pinned pins that restatement, pair by pair and bit
 for bit, against the oracle's own C functions (it needs no GPU).  t, u and v are compared bit for
 bit; NaN results (NaN or infinite inputs) compare as NaN, because NaN payloads are not portable
@@ -16,98 +16,8 @@ import pytest
 
 import oracle_lib as ol
 import random_scenes as rs
-
-F32 = np.float32
-EPS = F32(np.finfo(np.float32).eps)
-FLT_MAX = F32(np.finfo(np.float32).max)
-
-
-# ---- numpy restatement of the oracle's two primitive tests (vectorised over rays) -------------
-def _dot(a, b):  # vec.h:95-101 / orc_dot: sum = 0; sum += a[i] * b[i]
-    s = F32(0) + a[..., 0] * b[..., 0]
-    s = s + a[..., 1] * b[..., 1]
-    return s + a[..., 2] * b[..., 2]
-
-
-def _cross(a, b):  # vec.h:103-109
-    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1],
-                     a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
-                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
-
-
-def tri_test(o, d, v0, v1, v2):
-    """ray_triangle.h:7-46 for rays (o, d) against one triangle, every reject but `t2 >= t`:
-    -> (ok, t2, u2, v2)"""
-    with np.errstate(all="ignore"):
-        e1 = (v1 - v0).astype(F32)
-        e2 = (v2 - v0).astype(F32)
-        pv = _cross(d, np.broadcast_to(e2, d.shape))
-        det = _dot(np.broadcast_to(e1, d.shape), pv).astype(np.float64)
-        ok = ~((det > -EPS) & (det < EPS))
-        inv = 1.0 / det
-        tv = o - v0
-        u2 = (_dot(tv, pv).astype(np.float64) * inv).astype(F32)
-        ok &= ~((u2 < EPS) | (u2 > F32(1)))
-        qv = _cross(tv, np.broadcast_to(e1, d.shape))
-        v2 = (_dot(d, qv).astype(np.float64) * inv).astype(F32)
-        ok &= ~((v2 < EPS) | ((u2 + v2) > F32(1)))
-        t2 = (_dot(np.broadcast_to(e2, d.shape), qv).astype(np.float64) * inv).astype(F32)
-        ok &= ~(t2 < EPS)
-    return ok, t2, u2, v2
-
-
-def sph_test(o, d, sph):
-    """orc_intersect_sphere (oracle/rt_oracle.c) without `t2 >= t`: -> (ok, t2)"""
-    with np.errstate(all="ignore"):
-        oc = o - sph[:3]
-        b = _dot(oc, d)
-        cc = _dot(oc, oc) - sph[3] * sph[3]
-        disc = b * b - cc
-        ok = ~(disc < F32(0))
-        sq = np.sqrt(disc)
-        t2 = -b - sq
-        t2 = np.where(t2 < EPS, -b + sq, t2).astype(F32)
-        ok &= ~(t2 < EPS)
-    return ok, t2
-
-
-def ref_queries(d, o, dirs, tmax=None):
-    """closest hit and occlusion of every ray, in the reference's order, t carried from tmax"""
-    o = np.ascontiguousarray(o, F32)
-    dirs = np.ascontiguousarray(dirs, F32)
-    n = o.shape[0]
-    t0 = np.full(n, FLT_MAX, F32) if tmax is None else np.ascontiguousarray(tmax, F32).copy()
-    t = t0.copy()
-    uv = np.zeros((n, 2), F32)
-    geom = np.full(n, -1, np.int32)
-    prim = np.full(n, -1, np.int32)
-    occ = np.zeros(n, bool)
-    for gi, g in enumerate(d["geometry"]):
-        vert, fi = g["vertex"], g["face_index"]
-        for f in range(fi.shape[0]):
-            ok, t2, u2, v2 = tri_test(o, dirs, vert[fi[f, 0]], vert[fi[f, 1]], vert[fi[f, 2]])
-            occ |= ok & ~(t2 >= t0)
-            acc = ok & ~(t2 >= t)
-            t[acc] = t2[acc]
-            uv[acc, 0] = u2[acc]
-            uv[acc, 1] = v2[acc]
-            geom[acc] = gi
-            prim[acc] = f
-    for k, s in enumerate(d["spheres"]):
-        ok, t2 = sph_test(o, dirs, s)
-        occ |= ok & ~(t2 >= t0)
-        acc = ok & ~(t2 >= t)
-        t[acc] = t2[acc]
-        uv[acc] = 0
-        geom[acc] = -1
-        prim[acc] = k
-    return {"t": t, "geom": geom, "prim": prim, "uv": uv}, occ.astype(np.uint8)
-
-
-def same_bits(a, b):
-    a = np.ascontiguousarray(a, F32)
-    b = np.ascontiguousarray(b, F32)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+from ray_cases import box, surface_points
+from ray_oracle import EPS, F32, FLT_MAX, dot, normalize, ref_queries, same_bits, sph_test, tri_test
 
 
 def check_equal(got, occ, ref, ref_occ, what=""):
@@ -125,11 +35,6 @@ def check_equal(got, occ, ref, ref_occ, what=""):
 
 
 # ---- ray sets -------------------------------------------------------------------------------
-def normalize(v):  # vec.h:135 in fp32
-    v = np.ascontiguousarray(v, F32)
-    return (v / np.sqrt(_dot(v, v))[:, None]).astype(F32)
-
-
 def camera_rays(eye, look, W, H, vfov=60.0):
     """camera.h:31-34 get_ray over the pixel centres of a W x H image, in fp32 numpy"""
     import esctp1raytracer_amd as esc
@@ -141,18 +46,9 @@ def camera_rays(eye, look, W, H, vfov=60.0):
     return np.broadcast_to(c["origin"], dirs.shape).astype(F32).copy(), dirs
 
 
-def scene_box(d):
-    pts = [g["vertex"] for g in d["geometry"] if len(g["vertex"])]
-    if len(d["spheres"]):
-        s = d["spheres"]
-        pts += [s[:, :3] - s[:, 3:], s[:, :3] + s[:, 3:]]
-    p = np.concatenate(pts)
-    return p.min(0), p.max(0)
-
-
 def random_rays(d, n, seed):
     rng = np.random.default_rng(seed)
-    lo, hi = scene_box(d)
+    lo, hi = box(d)
     o = (lo + rng.uniform(0, 1, (n, 3)) * (hi - lo)).astype(F32)
     return o, normalize(rng.standard_normal((n, 3)))
 
@@ -243,38 +139,20 @@ def test_camera_rays_pinned_scenes(r, name):
     assert (ref["geom"] >= 0).sum() > 100
 
 
-def _surface_points(d, n, rng):
-    """points on triangles (barycentric) and on spheres"""
-    tris = [g["vertex"][g["face_index"]] for g in d["geometry"]]
-    tris = np.concatenate(tris) if tris else np.zeros((0, 3, 3), F32)
-    pts = []
-    if len(tris):
-        k = rng.integers(0, len(tris), n)
-        a, b = rng.uniform(0, 1, (2, n, 1))
-        sw = (a + b) > 1
-        a, b = np.where(sw, 1 - a, a), np.where(sw, 1 - b, b)
-        pts.append(tris[k, 0] + a * (tris[k, 1] - tris[k, 0]) + b * (tris[k, 2] - tris[k, 0]))
-    if len(d["spheres"]):
-        s = d["spheres"][rng.integers(0, len(d["spheres"]), n)]
-        pts.append(s[:, :3] + normalize(rng.standard_normal((n, 3))) * s[:, 3:])
-    p = np.concatenate(pts).astype(F32)
-    return p[rng.permutation(len(p))[:n]]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", [9, 18, 27, 3, 5, 36])
 def test_random_scenes_light_and_grazing_rays(r, seed):
     d, eye, look, W, H, vfov = rs.random_scene(seed)
     rng = np.random.default_rng(seed)
     n = rays_for_budget(d, 3000)
-    lo, hi = scene_box(d)
+    lo, hi = box(d)
     size = float(np.max(hi - lo))
     # surface points towards the lights (the light's first vertex, quirk S2), t bounded by the distance
-    p = _surface_points(d, n, rng)
+    p = surface_points(d, n, rng)
     lp = np.stack([d["geometry"][li]["vertex"][0] for li in d["light_sources"]])
     target = lp[rng.integers(0, len(lp), len(p))]
     dirs = normalize(target - p)
-    tmax = np.sqrt(_dot((target - p).astype(F32), (target - p).astype(F32))).astype(F32)
+    tmax = np.sqrt(dot((target - p).astype(F32), (target - p).astype(F32))).astype(F32)
     run_both(r, d, p, dirs, tmax, what=f"seed {seed} lights")
     # grazing: in the plane of a flat patch (or of y = const through the box), origins 1e-7 .. 1e-3
     # of the scene's size off it, directions nearly in it
@@ -294,7 +172,7 @@ def test_inside_spheres_and_far_origins(r):
     s = d["spheres"][rng.integers(0, len(d["spheres"]), n)]
     o = (s[:, :3] + rng.uniform(-0.5, 0.5, (n, 3)) * s[:, 3:]).astype(F32)
     run_both(r, d, o, normalize(rng.standard_normal((n, 3))), what="inside spheres")
-    lo, hi = scene_box(d)
+    lo, hi = box(d)
     c = (lo + hi) / 2
     far = (c + normalize(rng.standard_normal((n, 3))) * F32(20 * np.max(hi - lo))).astype(F32)
     dirs = normalize(c + rng.uniform(-0.3, 0.3, (n, 3)) * (hi - lo) - far)
@@ -479,7 +357,7 @@ def test_large_scenes_filtered_equals_exact(r, name):
     assert st["exact_rays"] == 0
     if name == "c4":
         assert st["exact_tests"] < 0.01 * n * P, st
-    lo, hi = scene_box(ol.scene_from_product(sc))
+    lo, hi = box(ol.scene_from_product(sc))
     rng = np.random.default_rng(13)
     m = 8192 if name != "c5" else 4096
     o = (lo + rng.uniform(0, 1, (m, 3)) * (hi - lo)).astype(F32)

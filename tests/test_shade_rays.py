@@ -4,9 +4,9 @@ against the frame kernels and the reference-pinned oracle.
 Three yardsticks:
   - camera rays: orc_camera_get_ray (camera.h:31-34) at s = (w + dx) / (W - 1), t = (h + dy) / (H - 1);
   - camera rays shaded: the frame itself (esc_render_rows), bit for bit, fp32 and u8;
-  - arbitrary rays: orc_render of pixel (0, 0) of a 2x2 frame whose camera is built by hand with
-    origin o and lower_left_corner a, so that its ray is (o, orc_camera_get_ray(cam, 0, 0)) and its
-    colour is scan_row's (main.cpp:698-791) for that ray.
+  - arbitrary rays: ray_oracle.ray_colours, orc_render of pixel (0, 0) of a 2x2 frame whose camera is
+    built by hand with origin o and lower_left_corner a, so that its ray is
+    (o, orc_camera_get_ray(cam, 0, 0)) and its colour is scan_row's (main.cpp:698-791) for that ray.
 NaN results compare as NaN (payloads are not portable between processors).
 """
 import ctypes as C
@@ -19,27 +19,10 @@ import pytest
 
 import oracle_lib as ol
 import random_scenes as rs
+from ray_cases import CORNELL_EYE, CORNELL_LOOK, box, ray_sets
+from ray_oracle import F32, assert_same, normalize, ray_colours
 
-F32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CORNELL_EYE, CORNELL_LOOK = (0, 1, 3.5), (0, 1, 0)
-
-
-def same_bits(a, b):
-    a = np.ascontiguousarray(a, F32)
-    b = np.ascontiguousarray(b, F32)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-
-
-def assert_same(a, b, what):
-    bad = ~same_bits(a, b)
-    assert not bad.any(), f"{what}: {int(bad.sum())} values differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
-def normalize(v):
-    v = np.ascontiguousarray(v, F32)
-    n = np.sqrt((F32(0) + v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
-    return (v / n[:, None]).astype(F32)
 
 
 @pytest.fixture(scope="module")
@@ -192,82 +175,6 @@ def test_face_modes_shadows_and_row_bands(esc, r):
 
 
 # ---- 3. arbitrary rays against the reference-pinned oracle ----------------------------------------
-def oracle_shade(d, origins, targets, fixed_face=0, shadows=True):
-    """per ray: a hand-built orc_camera (origin o_i, lower_left_corner a_i); its pixel (0, 0) of a 2x2
-    frame is scan_row's colour for (o_i, get_ray(cam, 0, 0)).  -> (dirs, rgb)"""
-    lib = ol.oracle()
-    osc = ol.OracleScene(d)
-    opts = ol.orc_options(1 if shadows else 0, ol.ORC_FACE_FIXED, fixed_face, 0, ol.ORC_QUIRK_ALL)
-    n = origins.shape[0]
-    dirs = np.zeros((n, 3), F32)
-    rgb = np.zeros((n, 3), F32)
-    img = np.zeros((2, 2, 3), F32)
-    cnt = ol.orc_counters()
-    out = np.zeros(3, F32)
-    for i in range(n):
-        cam = ol.orc_camera()
-        for k in range(3):
-            cam.origin[k] = float(origins[i, k])
-            cam.lower_left_corner[k] = float(targets[i, k])
-            cam.horizontal[k] = (1.0, 0.0, 0.0)[k]
-            cam.vertical[k] = (0.0, 1.0, 0.0)[k]
-        lib.orc_camera_get_ray(C.byref(cam), C.c_float(0), C.c_float(0), ol.fp(out))
-        dirs[i] = out
-        img[:] = 0
-        lib.orc_render(C.byref(osc.c), C.byref(cam), 2, 2, 0, 1, C.byref(opts), ol.fp(img), C.byref(cnt), 1)
-        rgb[i] = img[0, 0]
-    return dirs, rgb
-
-
-def _box(d):
-    pts = [g["vertex"] for g in d["geometry"] if len(g["vertex"])]
-    if len(d["spheres"]):
-        s = d["spheres"]
-        pts += [s[:, :3] - s[:, 3:], s[:, :3] + s[:, 3:]]
-    p = np.concatenate(pts)
-    return p.min(0), p.max(0)
-
-
-def _surface_points(d, n, rng):
-    tris = [g["vertex"][g["face_index"]] for g in d["geometry"] if len(g["face_index"])]
-    T = np.concatenate(tris) if tris else np.zeros((0, 3, 3), F32)
-    pts = []
-    if len(T):
-        k = rng.integers(0, len(T), n)
-        a, b = rng.uniform(0, 1, n), rng.uniform(0, 1, n)
-        flip = a + b > 1
-        a[flip], b[flip] = 1 - a[flip], 1 - b[flip]
-        pts.append(T[k, 0] + a[:, None] * (T[k, 1] - T[k, 0]) + b[:, None] * (T[k, 2] - T[k, 0]))
-    if len(d["spheres"]):
-        s = d["spheres"][rng.integers(0, len(d["spheres"]), n)]
-        pts.append(s[:, :3] + normalize(rng.standard_normal((n, 3))) * s[:, 3:])
-    p = np.concatenate(pts)
-    return p[rng.integers(0, len(p), n)].astype(F32)
-
-
-def ray_sets(d, rng, n):
-    lo, hi = _box(d)
-    ext = F32(max(1e-3, float(np.max(hi - lo))))
-    inside = (lo + rng.uniform(0, 1, (n, 3)) * (hi - lo)).astype(F32)
-    surf = _surface_points(d, n, rng)
-    sets = {
-        # orthographic bundle: one direction, origins on a plane in front of the scene
-        "ortho": ((lo + rng.uniform(0, 1, (n, 3)) * (hi - lo) + np.array([0, 0, 2]) * ext).astype(F32),
-                  None),
-        "from_surfaces": (surf, (surf + rng.standard_normal((n, 3)) * ext).astype(F32)),
-        "inside": (inside, _surface_points(d, n, rng)),
-        "far": ((lo + hi) / 2 + normalize(rng.standard_normal((n, 3))) * ext * F32(3e3), _surface_points(d, n, rng)),
-        # grazing: towards a surface point from a point nudged off it along the surface
-        "grazing": ((surf + rng.standard_normal((n, 3)) * ext * F32(1e-3)).astype(F32), _surface_points(d, n, rng)),
-    }
-    out = {}
-    for k, (o, a) in sets.items():
-        if a is None:
-            a = (o - np.array([0.02, 0.01, 1.0], F32) * ext).astype(F32)
-        out[k] = (np.ascontiguousarray(o, F32), np.ascontiguousarray(a, F32))
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed", ["cornell", 9, 18, 27, 3, 5, 14, 22])
 def test_arbitrary_rays_against_the_oracle(esc, r, seed):
@@ -279,7 +186,7 @@ def test_arbitrary_rays_against_the_oracle(esc, r, seed):
     rng = np.random.default_rng(7 if seed == "cornell" else seed)
     n = 96
     for name, (o, a) in ray_sets(d, rng, n).items():
-        dirs, want = oracle_shade(d, o, a)
+        dirs, want = ray_colours(d, o, a)
         got = r.shade(o, dirs, face_mode=esc.ESC_FACE_FIXED)
         assert_same(got["rgb"], want, f"{seed} {name}")
         ex = r.shade(o, dirs, face_mode=esc.ESC_FACE_FIXED, exact=True)
@@ -311,7 +218,7 @@ def test_quirk_s3_first_occluder(esc, r, n_filler):
     zs = np.linspace(0.004, 0.034, 7, dtype=F32)  # off the floor quad's diagonal (x = -z)
     o = np.stack([np.full(7, 3, F32), np.ones(7, F32), zs], 1).astype(F32)
     a = np.stack([np.zeros(7, F32), np.zeros(7, F32), zs], 1).astype(F32)
-    dirs, want = oracle_shade(d, o, a)
+    dirs, want = ray_colours(d, o, a)
     got = r.shade(o, dirs)
     assert_same(got["rgb"], want, "first occluder")
     assert (got["geom"] == 0).all()  # every ray hit the floor
@@ -337,7 +244,7 @@ def test_filtered_equals_exact(esc, r, name):
     o, dd = _cpu(o), _cpu(dd)
     if d is None:
         d = ol.scene_from_product(sc)
-    lo, hi = _box(d)
+    lo, hi = box(d)
     rng = np.random.default_rng(13)
     m = 8192 if name != "c5" else 2048
     oi = (lo + rng.uniform(0, 1, (m, 3)) * (hi - lo)).astype(F32)
@@ -372,7 +279,7 @@ def test_odd_inputs_match_exact(esc, r):
     r.upload(ol.scene_to_product(d))
     rng = np.random.default_rng(5)
     n = 4096
-    lo, hi = _box(d)
+    lo, hi = box(d)
     o = (lo + rng.uniform(0, 1, (n, 3)) * (hi - lo)).astype(F32)
     dirs = normalize(rng.standard_normal((n, 3)))
     dirs[::7] *= F32(2.0)

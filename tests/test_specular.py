@@ -10,7 +10,7 @@ says which base x = dot(N, H) and exponent that pixel has, and then
       With Ns in {16.5, 64, 120} one step of x moves x^Ns by >= Ns / 2 >= 8 steps, so this pins x;
   3b  with the measured powers fed back into the oracle as a table, frames of scenes with real specular
       materials are compared bit for bit, with no table miss; traced rays (the `_ns` cases of
-      test_trace_rays.py, a refraction case) take their table level by level from `shade`;
+      ray_cases.py, a refraction case) take their table level by level from `shade`;
   3c  with two and three lights the oracle's frames under powers 2 steps below and above the exact one
       bracket the GPU frame value by value (everything after the power is monotone for ks >= 0);
   4   where ks == +-0 the colour depends only on whether the power is finite and >= +0, so frames equal
@@ -20,7 +20,8 @@ import pytest
 
 import oracle_lib as ol
 import specular_lib as sl
-from test_trace_rays import oracle_trace, same_bits
+from ray_cases import TRACE_SETTINGS, camera_targets, product
+from ray_oracle import FRESNEL, MODE_NAME, REFRACT, assert_same, oracle_trace, stats_of
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -126,20 +127,21 @@ def gpu_shade_probe(r):
 
 @pytest.mark.parametrize("name", ["cornell_mixed_ns", "rand3_ns", "rand9_ns"])  # one light each (trace_ns_case)
 def test_ns_trace_cases_bit_for_bit_through_level_tables(esc, r, name):
-    """test_trace_rays.py's `_ns` cases at their settings: each level's rays (from the restatement; they
+    """ray_cases.py's `_ns` cases at their settings: each level's rays (from the restatement; they
     depend on no power) are shaded on the probe scene, which gives the table for oracle_trace"""
-    import test_trace_rays as tt
     d, o, a = sl.trace_ns_case(name)
     one_face = all(len(d["geometry"][g]["face_index"]) == 1 for g in d["light_sources"])
-    for max_depth, bias, shadows in tt.SETTINGS[1::3]:
+    for max_depth, bias, shadows in TRACE_SETTINGS[1::3]:
         bias = float(F32(bias))
-        with sl.recorded_levels(tt) as levels:
-            dirs, _, usable, counts, hits0 = tt.oracle_trace(d, o, a, max_depth, bias, 0, shadows)
-        assert usable.all() and counts[1] * 10 >= hits0 > 0 and counts[2] >= 1  # every ray is compared
+        levels, recording = sl.recorded_levels()
+        first = oracle_trace(d, o, a, max_depth, bias, shadows=shadows, colours=recording)
+        dirs, counts, hits0 = first["dirs"], first["depth_rays"], first["hit_rays0"]
+        assert first["usable"].all() and counts[1] * 10 >= hits0 > 0 and counts[2] >= 1  # every ray is compared
         table = sl.table_from_levels(d, levels, gpu_shade_probe(r))
-        with ol.pow_mode(ol.POW_TABLE, table=table), sl.recorded_levels(tt):
-            _, want, _, counts2, _ = tt.oracle_trace(d, o, a, max_depth, bias, 0, shadows)
+        with ol.pow_mode(ol.POW_TABLE, table=table):
+            again = oracle_trace(d, o, a, max_depth, bias, shadows=shadows, colours=sl.ray_colours)
             misses = ol.pow_misses()
+        want, counts2 = again["rgb"], again["depth_rays"]
         print(f"{name} depth {max_depth}: {len(o)} rays, levels {counts[:max_depth + 1]}, table of {len(table[0])} "
               f"powers, {misses} misses")
         assert misses == 0 and counts2 == counts
@@ -154,28 +156,27 @@ def test_ns_trace_cases_bit_for_bit_through_level_tables(esc, r, name):
 
 
 def test_refraction_with_exponents_bit_for_bit_through_level_tables(esc, r):
-    import test_transmission as tx
     d, o, a = sl.refraction_ns_case("slab")
     depth, bias, shadows = sl.REFRACTION_SETTING
     assert len(o) >= 64 and len(d["light_sources"]) == 1
-    for mode in (tx.REFRACT, tx.FRESNEL):
-        with sl.recorded_levels(tx) as levels:
-            first = tx.oracle_trace(d, o, a, depth, bias, mode, shadows)
+    for mode in (REFRACT, FRESNEL):
+        levels, recording = sl.recorded_levels()
+        first = oracle_trace(d, o, a, depth, bias, mode, shadows=shadows, colours=recording)
         assert first["usable"].all() and first["refracted"] > 0 and first["depth_rays"][2] > 0
         table = sl.table_from_levels(d, levels, gpu_shade_probe(r))
-        with ol.pow_mode(ol.POW_TABLE, table=table), sl.recorded_levels(tx):
-            want = tx.oracle_trace(d, o, a, depth, bias, mode, shadows)
+        with ol.pow_mode(ol.POW_TABLE, table=table):
+            want = oracle_trace(d, o, a, depth, bias, mode, shadows=shadows, colours=sl.ray_colours)
             misses = ol.pow_misses()
-        print(f"slab {tx.MODE_NAME[mode]}: {len(o)} rays, levels {want['depth_rays'][:depth + 1]}, table of "
+        print(f"slab {MODE_NAME[mode]}: {len(o)} rays, levels {want['depth_rays'][:depth + 1]}, table of "
               f"{len(table[0])} powers, {misses} misses")
         assert misses == 0 and want["depth_rays"] == first["depth_rays"]
-        r.upload(tx.product(d))
+        r.upload(product(d))
         for exact in (False, True):
-            got = r.trace(o, want["dirs"], max_depth=depth, bias=bias, shadows=shadows, seed=tx.SEED,
-                          pixel_base=tx.PIXEL_BASE, exact=exact, transmission=tx.MODE_NAME[mode])
+            got = r.trace(o, want["dirs"], max_depth=depth, bias=bias, shadows=shadows, seed=77,
+                          pixel_base=1234, exact=exact, transmission=MODE_NAME[mode])
             assert r.trace_stats()["depth_rays"] == want["depth_rays"]
-            assert r.transmit_stats() == tx.stats_of(want)
-            assert_same(got["rgb"], want["rgb"], f"slab {tx.MODE_NAME[mode]} exact {exact}")
+            assert r.transmit_stats() == stats_of(want)
+            assert_same(got["rgb"], want["rgb"], f"slab {MODE_NAME[mode]} exact {exact}")
             assert np.array_equal(got["rgb8"], ol.oracle_quantise(want["rgb"]))
 
 
@@ -201,20 +202,20 @@ def test_several_lights_inside_the_bracket(esc, r, name):
         out = (gpu < lo) | (gpu > hi)
         assert not out.any(), f"{name} {what}: {int(out.sum())} values outside the bracket"
     # trace at depth 3: every level's colour is such a frame value, weighted by products of ks >= 0
-    import test_trace_rays as tt
-    o, a = tt.camera_targets(eye, look, 24, 16)
+    o, a = camera_targets(eye, look, 24, 16)
     bias = float(F32(1e-4))
     # as case_rays does: only rays whose bounce directions the hand-built camera reproduces (no power has
     # a say in that), chosen by the oracle before the GPU is used; then every ray is compared
-    keep = oracle_trace(d, o, a, 3, bias)[2]
+    keep = oracle_trace(d, o, a, 3, bias)["usable"]
     print(f"{name}: {int(keep.sum())} of {len(keep)} camera rays kept for the trace")
     assert keep.sum() >= 192
     o, a = o[keep], a[keep]
     with ol.pow_mode(ol.POW_ROUNDED, -K):
-        dirs, tlo, usable, counts, _ = oracle_trace(d, o, a, 3, bias)
+        low = oracle_trace(d, o, a, 3, bias)
     with ol.pow_mode(ol.POW_ROUNDED, K):
-        _, thi, usable2, counts2, _ = oracle_trace(d, o, a, 3, bias)
-    assert usable.all() and usable2.all() and counts == counts2 and counts[3] > 0, counts
+        high = oracle_trace(d, o, a, 3, bias)
+    dirs, tlo, thi, counts = low["dirs"], low["rgb"], high["rgb"], low["depth_rays"]
+    assert low["usable"].all() and high["usable"].all() and counts == high["depth_rays"] and counts[3] > 0, counts
     got = r.trace(o, dirs, max_depth=3, bias=bias)
     assert r.trace_stats()["depth_rays"] == counts
     rgb = got["rgb"]
@@ -226,11 +227,6 @@ def test_several_lights_inside_the_bracket(esc, r, name):
 
 
 # ---- 4 ----------------------------------------------------------------------------------------------
-def assert_same(a, b, what):
-    bad = ~same_bits(a, b)
-    assert not bad.any(), f"{what}: {int(bad.sum())} values differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
 @pytest.mark.parametrize("name", ["cornell", "spheres", "odd_patches"])
 def test_the_skip_at_its_edges(esc, r, name):
     d, eye, look, W, H, vfov = sl.odd_patch_scene() if name == "odd_patches" else sl.edge_scene(name)
@@ -256,8 +252,9 @@ def test_the_skip_at_its_edges(esc, r, name):
     # multiplied by a weight and added (test_specular_cpu.py checks that the chosen rays do that)
     d, o, a = sl.edge_trace_rays()
     bias = float(F32(1e-4))
-    dirs, want, usable, counts, _ = oracle_trace(d, o, a, 2, bias)
-    assert usable.all() and counts[1] >= 20
+    res = oracle_trace(d, o, a, 2, bias)
+    dirs, want, counts = res["dirs"], res["rgb"], res["depth_rays"]
+    assert res["usable"].all() and counts[1] >= 20
     for exact in (False, True):
         got = r.trace(o, dirs, max_depth=2, bias=bias, exact=exact)
         assert r.trace_stats()["depth_rays"] == counts

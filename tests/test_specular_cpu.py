@@ -12,18 +12,13 @@ import pytest
 
 import oracle_lib as ol
 import specular_lib as sl
-from test_trace_rays import _dot, _normalize, closest_hits, normals_and_ks
-
-F32 = np.float32
-EPS = F32(np.finfo(np.float32).eps)
+from ray_cases import TRACE_SETTINGS
+from ray_oracle import (EPS, F32, FRESNEL, MODE_NAME, REFRACT, dot, normalize, normals_and_ks, oracle_trace,
+                        ref_queries, same_bits)
 
 
 def bits(a):
     return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
-def same_bits(a, b):
-    return (bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))
 
 
 def sphere_frame(**kw):
@@ -68,7 +63,7 @@ def restated_x(d, eye, look, W, H, seed):
                                    ol.fp(out))
             dirs[h * W + w] = out
     o = np.tile(np.array(list(cam.origin), F32), (H * W, 1))
-    hit = closest_hits(d, o, dirs)
+    hit, _ = ref_queries(d, o, dirs)
     N, _, has = normals_and_ks(d, hit, o, dirs)
     light = d["geometry"][d["light_sources"][0]]
     nf = len(light["face_index"])
@@ -76,9 +71,9 @@ def restated_x(d, eye, look, W, H, seed):
     P = (light["vertex"][face] + F32(0)).astype(F32)
     with np.errstate(all="ignore"):
         hitp = (o + (dirs * (hit["t"] - EPS).astype(F32)[:, None]).astype(F32)).astype(F32)
-        L = _normalize((P - hitp).astype(F32))
-        Hh = _normalize(((N + L).astype(F32) * F32(2)).astype(F32))
-        x = _dot(N, Hh)
+        L = normalize((P - hitp).astype(F32))
+        Hh = normalize(((N + L).astype(F32) * F32(2)).astype(F32))
+        x = dot(N, Hh)
     x[~has] = np.nan
     return x.reshape(H, W)
 
@@ -230,40 +225,40 @@ def libm_shade(probe, origins, targets, dirs, fixed_face, shadows):
 def test_level_tables_reproduce_the_traced_colours(name):
     """3b's gathering on the reference side alone: the table filled with glibc's powers, level by level,
     gives oracle_trace's own colours with no miss, so it holds every (x, Ns) a traced path meets"""
-    import test_trace_rays as tt
     d, o, a = sl.trace_ns_case(name)
-    for max_depth, bias, shadows in tt.SETTINGS[1::3]:
+    for max_depth, bias, shadows in TRACE_SETTINGS[1::3]:
         bias = float(F32(bias))
-        with sl.recorded_levels(tt) as levels:
-            dirs, want, usable, counts, _ = tt.oracle_trace(d, o, a, max_depth, bias, 0, shadows)
-        assert usable.all() and len(levels) == 1 + sum(c > 0 for c in counts[1:max_depth + 1])
+        levels, recording = sl.recorded_levels()
+        first = oracle_trace(d, o, a, max_depth, bias, shadows=shadows, colours=recording)
+        want, counts = first["rgb"], first["depth_rays"]
+        assert first["usable"].all() and len(levels) == 1 + sum(c > 0 for c in counts[1:max_depth + 1])
         table = sl.table_from_levels(d, levels, libm_shade)
-        with ol.pow_mode(ol.POW_TABLE, table=table), sl.recorded_levels(tt):
-            _, again, _, counts2, _ = tt.oracle_trace(d, o, a, max_depth, bias, 0, shadows)
+        with ol.pow_mode(ol.POW_TABLE, table=table):
+            again = oracle_trace(d, o, a, max_depth, bias, shadows=shadows, colours=sl.ray_colours)
             misses = ol.pow_misses()
-        assert tt.same_bits(tt.oracle_trace(d, o, a, max_depth, bias, 0, shadows)[1], want).all()  # ray_colours
+        # a zero `horizontal` (sl.ray_colours) changes no colour
+        assert same_bits(oracle_trace(d, o, a, max_depth, bias, shadows=shadows)["rgb"], want).all()
         print(f"{name} depth {max_depth}: {len(o)} rays, levels {counts[:max_depth + 1]}, table of {len(table[0])}")
-        assert misses == 0 and counts2 == counts and tt.same_bits(again, want).all()
+        assert misses == 0 and again["depth_rays"] == counts and same_bits(again["rgb"], want).all()
 
 
 def test_refraction_level_tables_reproduce_the_traced_colours():
-    import test_transmission as tx
     d, o, a = sl.refraction_ns_case("slab")
     depth, bias, shadows = sl.REFRACTION_SETTING
     assert len(o) >= 64
-    for mode in (tx.REFRACT, tx.FRESNEL):
-        with sl.recorded_levels(tx) as levels:
-            want = tx.oracle_trace(d, o, a, depth, bias, mode, shadows)
+    for mode in (REFRACT, FRESNEL):
+        levels, recording = sl.recorded_levels()
+        want = oracle_trace(d, o, a, depth, bias, mode, shadows=shadows, colours=recording)
         assert want["usable"].all() and want["refracted"] > 0 and want["depth_rays"][2] > 0
         table = sl.table_from_levels(d, levels, libm_shade)
-        with ol.pow_mode(ol.POW_TABLE, table=table), sl.recorded_levels(tx):
-            again = tx.oracle_trace(d, o, a, depth, bias, mode, shadows)
+        with ol.pow_mode(ol.POW_TABLE, table=table):
+            again = oracle_trace(d, o, a, depth, bias, mode, shadows=shadows, colours=sl.ray_colours)
             misses = ol.pow_misses()
-        assert misses == 0 and tx.same_bits(again["rgb"], want["rgb"]).all()
+        assert misses == 0 and same_bits(again["rgb"], want["rgb"]).all()
         with ol.pow_mode(ol.POW_ONE):  # the exponents matter on these paths
-            flat = tx.oracle_trace(d, o, a, depth, bias, mode, shadows)["rgb"]
-        n = int((~tx.same_bits(flat, want["rgb"])).any(axis=1).sum())
-        print(f"slab {tx.MODE_NAME[mode]}: {len(o)} rays, levels {want['depth_rays'][:depth + 1]}, table of "
+            flat = oracle_trace(d, o, a, depth, bias, mode, shadows=shadows)["rgb"]
+        n = int((~same_bits(flat, want["rgb"])).any(axis=1).sum())
+        print(f"slab {MODE_NAME[mode]}: {len(o)} rays, levels {want['depth_rays'][:depth + 1]}, table of "
               f"{len(table[0])}, {n} rays depend on a power")
         assert n >= 16  # the case is not vacuous: paths whose colour a power decides
 
@@ -272,12 +267,12 @@ def test_edge_scene_trace_carries_nan_through_a_weight():
     """section 4's traced rays, chosen here: the mirror strip on the floor sends level-1 rays to surfaces
     whose colour is NaN, so a NaN colour times a weight reaches rays whose own colour is finite"""
     d, o, a = sl.edge_trace_rays()
-    import test_trace_rays as tt
     bias = float(F32(1e-4))
-    _, c0, _, _, _ = tt.oracle_trace(d, o, a, 0, bias)
-    _, c2, usable, counts, _ = tt.oracle_trace(d, o, a, 2, bias)
-    assert usable.all() and counts[1] >= 20, counts
+    c0 = oracle_trace(d, o, a, 0, bias)["rgb"]
+    deep = oracle_trace(d, o, a, 2, bias)
+    c2, counts = deep["rgb"], deep["depth_rays"]
+    assert deep["usable"].all() and counts[1] >= 20, counts
     late = np.isnan(c2).any(axis=1) & np.isfinite(c0).all(axis=1)
-    changed = ~tt.same_bits(c2, c0).all(axis=1)
+    changed = ~same_bits(c2, c0).all(axis=1)
     print(f"edge trace: {len(o)} rays, levels {counts[:3]}, {int(changed.sum())} changed by level 1, {int(late.sum())} to NaN")
     assert late.sum() >= 3 and (changed & np.isfinite(c2).all(axis=1)).sum() >= 3

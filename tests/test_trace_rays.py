@@ -1,269 +1,24 @@
 """Mirror reflections on the GPU (esc_trace_rays / esc_render_traced, rt_trace.hip), bit for bit:
-depth 0 is esc_shade_rays; bounces against a CPU restatement made of existing oracle pieces (the
-index-order closest hit of test_ray_queries.py pinned to orc_intersect_*, orc_cross / orc_normalize
-for the normal, the reflection in numpy fp32 as include/esctp1_rt.h writes it, each level's colour
-by orc_render through a hand-built camera); large scenes composed from the public shade / intersect
-calls; odd inputs against exact mode; no interference with frames, queries and shading.
+depth 0 is esc_shade_rays; bounces against the CPU restatement of tests/ray_oracle.py (oracle_trace with
+transmission off: the index-order closest hit pinned to orc_intersect_*, orc_cross / orc_normalize for the
+normal, the reflection in numpy fp32 as include/esctp1_rt.h writes it, each level's colour by orc_render
+through a hand-built camera); large scenes composed from the public shade / intersect calls; odd inputs
+against exact mode; no interference with frames, queries and shading.
 
-How a level's colour comes out of orc_render for a bounce ray (o', d'): the hand-built camera's
-get_ray gives normalize(lower_left_corner - origin), and d' = normalize(x) with x = d - N*(2s).  With
-lower_left_corner = x * 2^40 the subtraction returns x * 2^40 exactly whenever every component of o'
-lies under half an ulp of the matching component of x * 2^40, and a power-of-two scale goes through
-normalize unchanged.  oracle_trace() checks the direction orc_camera_get_ray returns against d' for
-every ray and level, on the CPU.  case_rays() keeps only rays for which it agrees at every level of the
-deepest setting (chosen by the oracle alone, before anything runs on the GPU), and every case asserts
-that all of its rays are compared.
+The cases and their rays come from tests/ray_cases.py: trace_case_rays() keeps only rays for which the
+hand-built camera reproduces every bounce direction at every level of the deepest setting (chosen by the
+oracle alone, before anything runs on the GPU), and every case asserts that all of its rays are compared.
 
-powf: the device's and the host libm's differ in the last bit, which shade against orc_render shows at
-level 0 already (16 of 576 values on cornell_mixed, relative difference up to 1.6e-7).  The cases
-therefore come in two kinds, as tests/test_gpu_parity.py treats specular pixels: with Ns = 0 on the
-edited materials (pow(x, 0) is 1 on both sides) every bit is compared; with the materials' own and
-random Ns the tolerance of test_big_mesh_smooth_normals applies (rtol = atol = 1e-5, at least 90 % of
-the values bit-equal, u8 within 1), and depth_rays must still equal the oracle's counts exactly."""
-import ctypes as C
-
+powf: the device's and the host libm's differ in the last bit (ray_cases.py's docstring).  With Ns = 0
+on the edited materials every bit is compared; for the `_ns` cases the tolerance of
+test_big_mesh_smooth_normals applies (rtol = atol = 1e-5, at least 90 % of the values bit-equal, u8 within
+1), and depth_rays must still equal the oracle's counts exactly."""
 import numpy as np
 import pytest
 
 import oracle_lib as ol
-import random_scenes as rs
-
-F32 = np.float32
-FLT_MAX = F32(np.finfo(np.float32).max)
-CORNELL_EYE, CORNELL_LOOK = (0, 1, 3.5), (0, 1, 0)
-
-
-def same_bits(a, b):
-    a = np.ascontiguousarray(a, F32)
-    b = np.ascontiguousarray(b, F32)
-    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-
-
-def assert_same(a, b, what):
-    bad = ~same_bits(a, b)
-    assert not bad.any(), f"{what}: {int(bad.sum())} values differ, first at {np.argwhere(bad)[:4].tolist()}"
-
-
-# ---- the numpy index-order loop of test_ray_queries.py (pinned there to orc_intersect_*) ------------
-def _dot(a, b):  # vec.h:95-101 / orc_dot: sum = 0; sum += a[i] * b[i]
-    s = np.zeros(np.broadcast(a[..., 0], b[..., 0]).shape, F32)
-    for k in range(3):
-        s = (s + a[..., k] * b[..., k]).astype(F32)
-    return s
-
-
-def _cross(a, b):  # vec.h:103-109
-    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1],
-                     a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
-                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1).astype(F32)
-
-
-def _normalize(v):  # vec.h:135 in fp32
-    v = np.ascontiguousarray(v, F32)
-    return (v / np.sqrt(_dot(v, v))[..., None]).astype(F32)
-
-
-def closest_hits(d, o, dirs):
-    """closest hit of every ray in the reference's order: t, geometry, face / sphere, v"""
-    import test_ray_queries as q  # the restatement and its pin (test_numpy_restatement_pinned) live there
-    hit, _ = q.ref_queries(d, o, dirs)
-    return hit
-
-
-def normals_and_ks(d, hit, o, dirs):
-    """main.cpp:723-738 (quirk S1: u == 0) through orc_cross / orc_normalize, and the hit's ks"""
-    lib = ol.oracle()
-    n = o.shape[0]
-    N = np.zeros((n, 3), F32)
-    ks = np.zeros((n, 3), F32)
-    has = np.zeros(n, bool)
-    out = np.zeros(3, F32)
-    for i in range(n):
-        g, p = int(hit["geom"][i]), int(hit["prim"][i])
-        if g >= 0:
-            G = d["geometry"][g]
-            f = G["face_index"][p]
-            e1 = (G["vertex"][f[1]] - G["vertex"][f[0]]).astype(F32)
-            e2 = (G["vertex"][f[2]] - G["vertex"][f[0]]).astype(F32)
-            cr = np.zeros(3, F32)
-            lib.orc_cross(ol.fp(e1), ol.fp(e2), ol.fp(cr))
-            lib.orc_normalize(ol.fp(cr), ol.fp(out))
-            if len(G["normals"]):
-                u, v = F32(0), F32(hit["uv"][i, 1])
-                a = ((G["normals"][f[1]] * u).astype(F32) + (G["normals"][f[2]] * v).astype(F32)).astype(F32)
-                a = (a + (G["normals"][f[0]] * F32(F32(F32(1) - u) - v)).astype(F32)).astype(F32)
-                lib.orc_normalize(ol.fp(np.ascontiguousarray(a)), ol.fp(out))
-            N[i] = out
-            ks[i] = G["material"][6:9]
-            has[i] = True
-        elif p >= 0:
-            s = d["spheres"][p]
-            pt = ((o[i] + (dirs[i] * hit["t"][i]).astype(F32)).astype(F32) - s[:3]).astype(F32)
-            lib.orc_normalize(ol.fp(np.ascontiguousarray(pt)), ol.fp(out))
-            N[i] = out
-            ks[i] = d["sphere_materials"][p][6:9]
-            has[i] = True
-    return N, ks, has
-
-
-def oracle_colours(d, origins, llc, fixed_face=0, shadows=True):
-    """test_shade_rays.py::oracle_shade: per ray a hand-built orc_camera (origin o_i, lower_left_corner
-    llc_i); its pixel (0, 0) of a 2x2 frame is scan_row's colour for (o_i, get_ray(cam, 0, 0))"""
-    lib = ol.oracle()
-    osc = ol.OracleScene(d)
-    opts = ol.orc_options(1 if shadows else 0, ol.ORC_FACE_FIXED, fixed_face, 0, ol.ORC_QUIRK_ALL)
-    n = origins.shape[0]
-    dirs = np.zeros((n, 3), F32)
-    rgb = np.zeros((n, 3), F32)
-    img = np.zeros((2, 2, 3), F32)
-    cnt = ol.orc_counters()
-    out = np.zeros(3, F32)
-    for i in range(n):
-        cam = ol.orc_camera()
-        for k in range(3):
-            cam.origin[k] = float(origins[i, k])
-            cam.lower_left_corner[k] = float(llc[i, k])
-            cam.horizontal[k] = (1.0, 0.0, 0.0)[k]
-            cam.vertical[k] = (0.0, 1.0, 0.0)[k]
-        lib.orc_camera_get_ray(C.byref(cam), C.c_float(0), C.c_float(0), ol.fp(out))
-        dirs[i] = out
-        img[:] = 0
-        lib.orc_render(C.byref(osc.c), C.byref(cam), 2, 2, 0, 1, C.byref(opts), ol.fp(img), C.byref(cnt), 1)
-        rgb[i] = img[0, 0]
-    return dirs, rgb
-
-
-def reflect(o, dirs, t0, N, bias):
-    """the bounce of include/esctp1_rt.h in numpy fp32: (o', x, d') with d' = normalize(x)"""
-    s = _dot(dirs, N)
-    Nf = np.where((s > 0)[:, None], -N, N).astype(F32)
-    o2 = ((o + (dirs * t0[:, None]).astype(F32)).astype(F32) + (Nf * F32(bias)).astype(F32)).astype(F32)
-    x = (dirs - (N * (F32(2) * s).astype(F32)[:, None]).astype(F32)).astype(F32)
-    with np.errstate(all="ignore"):
-        return o2, x, _normalize(x)
-
-
-def oracle_trace(d, o, targets, max_depth, bias, fixed_face=0, shadows=True):
-    """-> (level-0 directions, C, usable mask, rays per level, hit rays at level 0)"""
-    n = o.shape[0]
-    dirs0, c = oracle_colours(d, o, targets, fixed_face, shadows)
-    Cc = c.copy()
-    usable = np.ones(n, bool)
-    counts = [n] + [0] * 16
-    idx = np.arange(n)
-    co, cd, w = o.copy(), dirs0.copy(), np.ones((n, 3), F32)
-    hits0 = 0
-    with np.errstate(all="ignore"):
-        for k in range(max_depth):
-            if len(idx) == 0:
-                break
-            hit = closest_hits(d, co, cd)
-            N, ks, has = normals_and_ks(d, hit, co, cd)
-            if k == 0:
-                hits0 = int(has.sum())
-            w = (w * ks).astype(F32)
-            go = has & ((w[:, 0] > 0) | (w[:, 1] > 0) | (w[:, 2] > 0))
-            o2, x, d2 = reflect(co, cd, hit["t"], N, bias)
-            idx, co, cd, w, x = idx[go], o2[go], d2[go], w[go], x[go]
-            counts[k + 1] = len(idx)
-            if len(idx) == 0:
-                break
-            got_d, c = oracle_colours(d, co, (x * F32(2.0 ** 40)).astype(F32), fixed_face, shadows)
-            usable[idx[~same_bits(got_d, cd).all(axis=1)]] = False
-            Cc[idx] = (Cc[idx] + (w * c).astype(F32)).astype(F32)
-    return dirs0, Cc, usable, counts, hits0
-
-
-# ---- scenes ------------------------------------------------------------------------------------------
-def with_ks(d, seed, share=0.6, ns_zero=True):
-    """a share of the materials gets ks > 0, one a zero channel, one NaN, one negative; Ns = 0 or random
-    (the module docstring says why)"""
-    rng = np.random.default_rng(seed)
-    mats = [g["material"] for g in d["geometry"]] + list(d["sphere_materials"])
-    pick = [m for m in mats if rng.uniform() < share]
-    for j, m in enumerate(pick):
-        m[6:9] = rng.uniform(0.3, 0.95, 3)
-        m[12] = 0.0 if ns_zero else rng.uniform(1.0, 60.0)
-        if j % 7 == 3:
-            m[6 + j % 3] = 0.0
-        if j % 23 == 11:
-            m[6:9] = np.nan
-        if j % 23 == 17:
-            m[7] = -0.5
-    return d
-
-
-def camera_targets(eye, look, W, H):
-    """origins and lower-left-corner style targets of a W x H frame's rays (any point on the ray)"""
-    import esctp1raytracer_amd as esc
-    cam = esc.Camera.for_image(eye, look, W, H).c
-    o = np.tile(np.array(list(cam.origin), F32), (W * H, 1))
-    llc, hz, vt = (np.array(list(v), F32) for v in (cam.lower_left_corner, cam.horizontal, cam.vertical))
-    t = []
-    for h in range(H):
-        for w_ in range(W):
-            s, tt = F32(w_) / F32(W - 1), F32(h) / F32(H - 1)
-            t.append(((llc + (hz * s).astype(F32)).astype(F32) + (vt * tt).astype(F32)).astype(F32))
-    return o, np.array(t, F32)
-
-
-_CASE_CACHE = {}
-
-
-def case_rays(name):
-    """-> (scene dict, origins, targets): chosen on the CPU so that the oracle itself bounces, and so that
-    the hand-built camera reproduces every bounce direction down to level 5 (module docstring)"""
-    if name not in _CASE_CACHE:
-        d, o, a = _case_rays(name)
-        keep = np.ones(len(o), bool)
-        for bias, shadows in {(b, s_) for _, b, s_ in SETTINGS}:
-            keep &= oracle_trace(d, o, a, 5, float(F32(bias)), 0, shadows)[2]
-        _CASE_CACHE[name] = (d, o[keep], a[keep])
-    return _CASE_CACHE[name]
-
-
-def _case_rays(name):
-    ns_zero = not name.endswith("_ns")
-    name = name[:-3] if name.endswith("_ns") else name
-    rng = np.random.default_rng(11)
-    if name in ("mirror_camera", "mirror_floor_camera"):
-        d = ol.load_dump("CornellBox-Mirror")
-        if name == "mirror_floor_camera":  # the floor reflects too, so that paths go past level 1
-            d["geometry"][0]["material"][6:9] = (0.5, 0.4, 0.0)
-            d["geometry"][0]["material"][12] = 0.0  # see with_ks
-        V = d["geometry"][5]["vertex"]
-        c = (V.min(0) + V.max(0)) / 2
-        o, a = camera_targets(tuple(float(x) for x in c + np.array([0.5, 0.3, 1.6])), tuple(float(x) for x in c),
-                              16, 12)
-        return d, o, a
-    if name == "mirror_block":
-        d = ol.load_dump("CornellBox-Mirror")
-        G = d["geometry"][5]  # ks = 0.95, Ns = 1000: the tall block
-        T = G["vertex"][G["face_index"]]
-        k = rng.integers(0, len(T), 160)
-        a, b = rng.uniform(0.05, 0.45, 160), rng.uniform(0.05, 0.45, 160)
-        pts = (T[k, 0] + a[:, None] * (T[k, 1] - T[k, 0]) + b[:, None] * (T[k, 2] - T[k, 0])).astype(F32)
-        o = (np.array([0, 1, 0.9], F32) + rng.uniform(-0.6, 0.6, (160, 3))).astype(F32)
-        return d, o, pts
-    if name == "cornell_mixed":
-        d = with_ks(ol.load_dump("CornellBox-Original"), 5, share=0.8, ns_zero=ns_zero)
-        o, a = camera_targets(CORNELL_EYE, CORNELL_LOOK, 16, 12)
-        return d, o, a
-    seed = int(name[4:])
-    d, eye, look, _, _, _ = rs.random_scene(seed)
-    d = with_ks(d, seed, ns_zero=ns_zero)
-    import test_shade_rays as ts
-    o, a = ts.ray_sets(d, rng, 64)["inside"]
-    o2, a2 = camera_targets(eye, look, 12, 8)
-    return d, np.concatenate([o, o2]), np.concatenate([a, a2])
-
-
-# the unedited Mirror scene has one reflecting (convex) block: its paths end at level 1
-SETTINGS = [(1, 0.0, True), (2, 1e-4, True), (5, 0.5, False), (2, 0.0, False), (5, 1e-4, True)]
-CASES = [("mirror_camera", 1, 0.0, True), ("mirror_camera", 1, 1e-4, False), ("mirror_block", 1, 0.0, True),
-         ("mirror_block", 1, 0.5, False)] + \
-        [(n, *s) for n in ("mirror_floor_camera", "cornell_mixed", "rand3", "rand5", "rand9") for s in SETTINGS] + \
-        [(n, *s) for n in ("cornell_mixed_ns", "rand3_ns", "rand9_ns") for s in SETTINGS[1::3]]
+from ray_cases import CORNELL_EYE, CORNELL_LOOK, TRACE_CASES, trace_case_rays, with_ks
+from ray_oracle import F32, assert_same, cross, normalize, oracle_trace, reflect, same_bits
 
 
 @pytest.fixture(scope="module")
@@ -281,16 +36,17 @@ def r(esc):
 
 # ---- 2. bounces against the CPU restatement ---------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,max_depth,bias,shadows", CASES)
+@pytest.mark.parametrize("name,max_depth,bias,shadows", TRACE_CASES)
 def test_bounces_against_the_oracle(esc, r, name, max_depth, bias, shadows):
-    d, o, a = case_rays(name)
+    d, o, a = trace_case_rays(name)
     bias = float(F32(bias))
-    dirs, want, usable, counts, hits0 = oracle_trace(d, o, a, max_depth, bias, 0, shadows)
+    res = oracle_trace(d, o, a, max_depth, bias, shadows=shadows)
+    dirs, want, usable, counts, hits0 = (res[k] for k in ("dirs", "rgb", "usable", "depth_rays", "hit_rays0"))
     # the oracle alone must bounce, or the comparison below shows nothing
     assert hits0 > 0 and counts[1] * 10 >= hits0, (counts, hits0)
     if max_depth >= 2:
         assert counts[2] >= 1, counts
-    assert usable.all(), np.flatnonzero(~usable).tolist()  # every ray is compared (see case_rays)
+    assert usable.all(), np.flatnonzero(~usable).tolist()  # every ray is compared (see trace_case_rays)
     r.upload(ol.scene_to_product(d))
     one_face = all(len(d["geometry"][g]["face_index"]) == 1 for g in d["light_sources"])
     for mode in (esc.ESC_FACE_FIXED, esc.ESC_FACE_HASH):
@@ -336,7 +92,7 @@ def test_depth_zero_is_shade(esc, r, name):
     o, d = o.cpu().numpy(), d.cpu().numpy()
     rng = np.random.default_rng(3)
     o2 = (o[0] + rng.standard_normal((4096, 3))).astype(F32)
-    d2 = _normalize(rng.standard_normal((4096, 3)))
+    d2 = normalize(rng.standard_normal((4096, 3)))
     for oo, dd, what in ((o, d, "camera"), (o2, d2, "arbitrary")):
         for mode in (esc.ESC_FACE_FIXED, esc.ESC_FACE_HASH):
             want = r.shade(oo, dd, face_mode=mode, seed=9, pixel_base=5)
@@ -438,7 +194,7 @@ def test_c4_4k_composed_from_shade_and_intersect(esc, r):
             ks[sph] = d["sphere_materials"][sh["prim"][sph]][:, 6:9]
             N = np.zeros((len(idx), 3), F32)
             pt = ((o + (dd * sh["t"][:, None]).astype(F32)).astype(F32)[sph] - d["spheres"][sh["prim"][sph], :3])
-            N[sph] = _normalize(pt.astype(F32))
+            N[sph] = normalize(pt.astype(F32))
             w = (w * ks).astype(F32)
             go = sph & ((w[:, 0] > 0) | (w[:, 1] > 0) | (w[:, 2] > 0))
             o2, _, d2 = reflect(o, dd, sh["t"], N, bias)
@@ -464,11 +220,11 @@ def _tri_normals(G, prim, v):
     """main.cpp:728-738 (quirk S1: u == 0) for hits on geometry G, vectorised in fp32"""
     f = G["face_index"][prim]
     V = G["vertex"]
-    N = _normalize(_cross((V[f[:, 1]] - V[f[:, 0]]).astype(F32), (V[f[:, 2]] - V[f[:, 0]]).astype(F32)))
+    N = normalize(cross((V[f[:, 1]] - V[f[:, 0]]).astype(F32), (V[f[:, 2]] - V[f[:, 0]]).astype(F32)))
     if len(G["normals"]):
         n = G["normals"]
         a = ((n[f[:, 1]] * F32(0)).astype(F32) + (n[f[:, 2]] * v[:, None]).astype(F32)).astype(F32)
-        N = _normalize((a + (n[f[:, 0]] * ((F32(1) - F32(0)) - v)[:, None]).astype(F32)).astype(F32))
+        N = normalize((a + (n[f[:, 0]] * ((F32(1) - F32(0)) - v)[:, None]).astype(F32)).astype(F32))
     return N
 
 
@@ -532,7 +288,7 @@ def test_odd_inputs_match_exact(esc, r):
     rng = np.random.default_rng(2)
     n = 4096
     o = (np.array([0, 1, 0.5], F32) + rng.uniform(-0.4, 0.4, (n, 3))).astype(F32)
-    dd = _normalize(rng.standard_normal((n, 3)))
+    dd = normalize(rng.standard_normal((n, 3)))
     odd = [np.zeros(3), np.array([3.0, 0, 0]), np.array([1e30, 0, 0]), np.array([np.nan, 0, 1]),
            np.array([np.inf, 0, 0]), np.array([0, -1e-30, 0])]
     for j, v in enumerate(odd):

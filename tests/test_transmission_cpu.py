@@ -14,7 +14,7 @@ import pytest
 import esctp1raytracer_amd as esc
 import oracle_lib as ol
 from esctp1raytracer_amd import _capi
-from test_host_surface import models  # noqa: F401  (the fixture that unpacks cornell_models.tar.gz)
+from model_files import models  # noqa: F401  (the fixture that unpacks cornell_models.tar.gz)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VIEWER = os.path.join(ROOT, "bin", "ESCViewer2021")
