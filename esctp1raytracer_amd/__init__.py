@@ -597,6 +597,42 @@ class Renderer:
         check(self._lib.esc_last_shade_stats(self._h, C.byref(s)))
         return {k: getattr(s, k) for k in ("rays", "hit_rays", "shadow_rays", "exact_rays", "exact_tests")}
 
+    def render_adaptive(self, camera, W, H, spp, threshold, *, band_rows=0, want_u8=False, want_mask=False,
+                        shadows=True, face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False):
+        """Adaptively anti-aliased frame (esc_render_adaptive): the 1-sample frame, with render_supersampled's
+        spp-sample value in every pixel that differs from a 4-neighbour by more than `threshold` in some
+        channel.  band_rows: 0 (automatic) or the rows refined per band (a memory knob; same image).
+        Returns numpy fp32 (H, W, 3), then the quantised bytes (want_u8) and the uint8 (H, W) mask
+        (want_mask) when asked for.  Synchronous."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        img = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        u8 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if want_u8 else None
+        mask = torch.empty((H, W), dtype=torch.uint8, device=dev) if want_mask else None
+        o = _options(shadows, face_mode, fixed_face, seed, ESC_STAGE_AUTO, 0,
+                     ESC_RENDER_EXACT_ONLY if exact else 0)
+        a = _capi.esc_adaptive_options(int(spp), float(threshold), int(band_rows), 0)
+        torch.cuda.current_stream(dev).synchronize()  # the buffers were made on torch's stream
+        check(self._lib.esc_render_adaptive(self._h, C.byref(camera.c), W, H, C.byref(o), C.byref(a),
+                                            C.c_void_p(img.data_ptr()),
+                                            None if u8 is None else C.c_void_p(u8.data_ptr()),
+                                            None if mask is None else C.c_void_p(mask.data_ptr())))
+        self.synchronize()
+        out = [img.cpu().numpy()]
+        if want_u8:
+            out.append(u8.cpu().numpy())
+        if want_mask:
+            out.append(mask.cpu().numpy())
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def adaptive_stats(self):
+        """Counts of the last render_adaptive call: pixels, refined_pixels, samples (refined_pixels * spp)
+        and, of the refinement rays, hit_rays, shadow_rays, exact_rays, exact_tests.  Synchronises."""
+        s = _capi.esc_adaptive_stats()
+        check(self._lib.esc_last_adaptive_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k in ("pixels", "refined_pixels", "samples", "hit_rays", "shadow_rays",
+                                                "exact_rays", "exact_tests")}
+
     def trace_rays(self, origins, dirs, rgb, *, max_depth, bias, rgb8=None, pixel_base=0, shadows=True,
                    face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False, transmission="off"):
         """Mirror reflections (esc_trace_rays): shade_rays' colour plus up to max_depth (0..16) specular

@@ -112,6 +112,16 @@ class esc_transmit_stats(C.Structure):  # 24 bytes
     _fields_ = [("refracted", C.c_uint64), ("fresnel_reflected", C.c_uint64), ("total_internal", C.c_uint64)]
 
 
+class esc_adaptive_options(C.Structure):  # 16 bytes
+    _fields_ = [("spp", C.c_int32), ("threshold", C.c_float), ("band_rows", C.c_int32), ("reserved", C.c_int32)]
+
+
+class esc_adaptive_stats(C.Structure):  # 56 bytes
+    _fields_ = [("pixels", C.c_uint64), ("refined_pixels", C.c_uint64), ("samples", C.c_uint64),
+                ("hit_rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("exact_rays", C.c_uint64),
+                ("exact_tests", C.c_uint64)]
+
+
 class esc_bvh_node(C.Structure):  # 64 bytes
     _fields_ = [("lo0", C.c_float * 3), ("hi0", C.c_float * 3), ("lo1", C.c_float * 3),
                 ("hi1", C.c_float * 3), ("child", C.c_int32 * 2), ("minkey", C.c_uint32 * 2)]
@@ -209,6 +219,10 @@ SIGNATURES = {
     "esc_last_shade_stats": (C.c_int, [_P, C.POINTER(esc_shade_stats)]),
     "esc_render_supersampled": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
                                           C.c_int32, C.POINTER(esc_render_options), _P, _P]),
+    "esc_render_adaptive": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
+                                      C.POINTER(esc_render_options), C.POINTER(esc_adaptive_options),
+                                      _P, _P, _P]),
+    "esc_last_adaptive_stats": (C.c_int, [_P, C.POINTER(esc_adaptive_stats)]),
     "esc_trace_rays": (C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, C.POINTER(esc_render_options),
                                  C.c_int32, C.c_float, _P, _P]),
     "esc_render_traced": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32, C.c_int32,

@@ -15,6 +15,7 @@
 
 #include "../host/accel_build.h"
 #include "../host/scene.h"
+#include "rt_adaptive.h"
 #include "rt_device.h"
 #include "rt_query.h"
 #include "rt_shade_rays.h"
@@ -51,6 +52,9 @@ extern "C" int esc_launch_camera_rays(const esc::CameraRayParams *p, hipStream_t
 extern "C" int esc_launch_ss_accumulate(float *acc, const float *rgb, int64_t n, int first, hipStream_t stream);
 extern "C" int esc_launch_ss_finish(float *img, uint8_t *u8, int64_t n, float spp, hipStream_t stream);
 extern "C" int esc_launch_trace_level(const esc::TraceParams *p, hipStream_t stream);
+extern "C" int esc_launch_adaptive_mask(const esc::AdaptiveMaskParams *p, hipStream_t stream);
+extern "C" int esc_launch_adaptive_list(const esc::AdaptiveListParams *p, hipStream_t stream);
+extern "C" int esc_launch_adaptive_refine(const esc::AdaptiveRefineParams *p, hipStream_t stream);
 extern "C" int esc_launch_assemble(const void *gathered, void *frame, size_t rank_pitch_bytes,
                                    int n_ranks, int H, int strip_rows, size_t row_bytes,
                                    hipStream_t stream);
@@ -174,6 +178,14 @@ struct esc_context {
   // whether any of its entries is transmissive: only then do the TRANSMIT kernels run
   float *d_transmit = nullptr;
   bool any_transmissive = false;
+  // esc_render_adaptive (rt_adaptive.hip): esc_adaptive_stats' device counters + the list's counter,
+  // and the scratch (grow-only): 4 bytes per list slot of a band, then 1 byte per pixel for the mask
+  // when the caller passes none.  ad_pixels / ad_spp: the last call's frame and spp, for the stats
+  unsigned long long *d_astats = nullptr;
+  uint8_t *d_ad = nullptr;
+  size_t ad_bytes = 0;
+  uint64_t ad_pixels = 0;
+  int32_t ad_spp = 0;
 };
 
 namespace {
@@ -1100,7 +1112,7 @@ void esc_context_destroy(esc_context *ctx) {
                   ctx->d_tri_boxes, ctx->d_sph_boxes, ctx->d_bin_hdr, ctx->d_bin_tri_ids,
                   ctx->d_bin_sph_ids, ctx->lbins.face_hdr, ctx->lbins.counts, ctx->lbins.tri_ids,
                   ctx->lbins.sph_ids, ctx->d_qstats, ctx->d_sstats, ctx->d_ss, ctx->d_tstats, ctx->d_tr,
-                  ctx->d_transmit};
+                  ctx->d_transmit, ctx->d_astats, ctx->d_ad};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t ev : ctx->ev)
@@ -2500,6 +2512,129 @@ int esc_render_supersampled(esc_context *ctx, const esc_camera *cam, int32_t W, 
   return ESC_OK;
 }
 
+
+// ---- adaptive supersampling (rt_adaptive.hip) ------------------------------------------------------
+constexpr int kAdaptiveWords = esc::kAdaptiveStats + 1; // esc_adaptive_stats' counters, then the list's counter
+
+int esc_render_adaptive(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
+                        const esc_render_options *opts, const esc_adaptive_options *aopts, float *d_image,
+                        uint8_t *d_u8, uint8_t *d_mask) {
+  const char *fn = "esc_render_adaptive";
+  if (ctx && !aopts) {
+    set_error(std::string(fn) + ": adaptive options are null");
+    return ESC_ERR_INVALID;
+  }
+  int nn = 0;
+  int rc = frame_args_ok(ctx, fn, cam, W, H, aopts ? aopts->spp : 1, opts, d_image, nn);
+  if (rc) return rc;
+  if (!(aopts->threshold >= 0.f) || !std::isfinite(aopts->threshold)) {
+    set_error(std::string(fn) + ": threshold must be a finite number >= 0");
+    return ESC_ERR_INVALID;
+  }
+  if (aopts->reserved != 0) {
+    set_error(std::string(fn) + ": reserved must be 0");
+    return ESC_ERR_INVALID;
+  }
+  if (aopts->band_rows < 0) {
+    set_error(std::string(fn) + ": band_rows must be 0 (automatic) or a positive row count");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  // bands of whole rows (of pixels when one row does not fit) whose list stays within the scratch budget
+  const int64_t total = (int64_t)W * H;
+  int64_t band = std::min<int64_t>(total, (int64_t)(kSsScratchBytes / sizeof(uint32_t)));
+  if (band >= W) band -= band % W;
+  if (aopts->band_rows > 0) band = std::min<int64_t>(total, (int64_t)aopts->band_rows * W);
+  const size_t list_bytes = ((size_t)band * sizeof(uint32_t) + 255) & ~(size_t)255;
+  const size_t need = list_bytes + (d_mask ? 0 : (size_t)total);
+  if (ctx->ad_bytes < need) {
+    if (ctx->d_ad) HIP_TRY(hipFree(ctx->d_ad));
+    ctx->d_ad = nullptr;
+    ctx->ad_bytes = 0;
+    HIP_TRY(hipMalloc((void **)&ctx->d_ad, need));
+    ctx->ad_bytes = need;
+  }
+  if (!ctx->d_astats) HIP_TRY(hipMalloc((void **)&ctx->d_astats, kAdaptiveWords * sizeof(unsigned long long)));
+  uint32_t *d_list = (uint32_t *)ctx->d_ad;
+  uint8_t *mask = d_mask ? d_mask : ctx->d_ad + list_bytes;
+  uint32_t *d_count = (uint32_t *)(ctx->d_astats + esc::kAdaptiveStats);
+
+  // 1. the base frame B, on the frame path
+  if ((rc = esc_render_rows(ctx, cam, W, H, 0, H, opts, d_image, d_u8))) return rc;
+  HIP_TRY(hipMemsetAsync(ctx->d_astats, 0, kAdaptiveWords * sizeof(unsigned long long), ctx->stream));
+  ctx->ad_pixels = (uint64_t)total;
+  ctx->ad_spp = aopts->spp;
+  // 2. the mask of the whole frame, before any pixel is refined in place
+  esc::AdaptiveMaskParams mp;
+  std::memset(&mp, 0, sizeof(mp));
+  mp.image = d_image;
+  mp.mask = mask;
+  mp.W = W;
+  mp.H = H;
+  mp.threshold = aopts->threshold;
+  int e = esc_launch_adaptive_mask(&mp, ctx->stream);
+  if (e) {
+    set_error(std::string(fn) + ": k_adaptive_mask launch: " + hipGetErrorString((hipError_t)e));
+    return ESC_ERR_HIP;
+  }
+  // 3. per band: list the masked pixels, refine the listed ones
+  esc::AdaptiveRefineParams rp;
+  std::memset(&rp, 0, sizeof(rp));
+  shade_params(ctx, rp.s, 0, nullptr, nullptr, 0, opts, opts->seed, d_image, d_u8);
+  rp.s.stats = ctx->d_astats;
+  std::memcpy(rp.origin, cam->origin, 12);
+  std::memcpy(rp.llc, cam->lower_left_corner, 12);
+  std::memcpy(rp.horizontal, cam->horizontal, 12);
+  std::memcpy(rp.vertical, cam->vertical, 12);
+  rp.W = W;
+  rp.H = H;
+  rp.spp = aopts->spp;
+  rp.nn = nn;
+  rp.list = d_list;
+  rp.count = d_count;
+  for (int64_t p0 = 0; p0 < total; p0 += band) {
+    const int64_t n = std::min(band, total - p0);
+    if (p0 > 0) HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint32_t), ctx->stream));
+    esc::AdaptiveListParams lp;
+    std::memset(&lp, 0, sizeof(lp));
+    lp.mask = mask;
+    lp.list = d_list;
+    lp.count = d_count;
+    lp.pix0 = p0;
+    lp.n = n;
+    if ((e = esc_launch_adaptive_list(&lp, ctx->stream))) {
+      set_error(std::string(fn) + ": k_adaptive_list launch: " + hipGetErrorString((hipError_t)e));
+      return ESC_ERR_HIP;
+    }
+    rp.s.q.n = n;
+    if ((e = esc_launch_adaptive_refine(&rp, ctx->stream))) {
+      set_error(std::string(fn) + ": k_adaptive_refine launch: " + hipGetErrorString((hipError_t)e));
+      return ESC_ERR_HIP;
+    }
+  }
+  return ESC_OK;
+}
+
+int esc_last_adaptive_stats(esc_context *ctx, esc_adaptive_stats *out) {
+  if (!ctx || !out) {
+    set_error(!ctx ? "esc_last_adaptive_stats: ctx is null" : "esc_last_adaptive_stats: out is null");
+    return ESC_ERR_INVALID;
+  }
+  unsigned long long h[esc::kAdaptiveStats] = {0, 0, 0, 0, 0};
+  if (ctx->d_astats) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_astats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  out->pixels = ctx->ad_pixels;
+  out->refined_pixels = h[0];
+  out->samples = h[0] * (uint64_t)ctx->ad_spp;
+  out->hit_rays = h[1];
+  out->shadow_rays = h[2];
+  out->exact_rays = h[3];
+  out->exact_tests = h[4];
+  return ESC_OK;
+}
 
 // ---- mirror reflections (rt_trace.hip) -------------------------------------------------------------
 constexpr int kTraceStatWords = esc::kTraceStats + esc::kTransmitStats; // esc_trace_stats, esc_transmit_stats

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_camera_ray.h"
 #include "rt_shade_body.h"
 
 namespace esc {
@@ -78,9 +79,7 @@ __global__ __launch_bounds__(256) void k_camera_rays(const CameraRayParams p) {
   const float dx = p.offsets ? p.offsets[2 * i] : p.dx;
   const float dy = p.offsets ? p.offsets[2 * i + 1] : p.dy;
   const f3 origin = mk(p.origin[0], p.origin[1], p.origin[2]);
-  const float is = ((float)w + dx) / (float)(p.W - 1);
-  const float it = ((float)h + dy) / (float)(p.H - 1);
-  const f3 dir = normalize(((ld3(p.llc) + ld3(p.horizontal) * is) + ld3(p.vertical) * it) - origin);
+  const f3 dir = camera_ray_dir(origin, p.llc, p.horizontal, p.vertical, p.W, p.H, w, h, dx, dy);
   p.orig[3 * i] = origin.x;
   p.orig[3 * i + 1] = origin.y;
   p.orig[3 * i + 2] = origin.z;

@@ -31,6 +31,9 @@
 //   --spp N       anti-aliased frame: N = n*n samples per pixel on a regular sub-pixel grid, n in 1..8
 //                 (esc_render_supersampled; one GPU, not with --ispc or --bvh).  The frame is the mean
 //                 of the samples; the PPM is written as usual
+//   --adaptive T  with --spp: only the pixels that differ from a 4-neighbour by more than T (finite, >= 0) in
+//                 some channel of the 1-sample frame get the N samples; the others keep the frame's value
+//                 (esc_render_adaptive).  Not with --bounces
 //   --bounces N   mirror reflections: up to N (0..16) specular bounces weighted by the materials' ks
 //                 (esc_render_traced; combinable with --spp, otherwise under --spp's restrictions)
 //   --bias X      with --bounces: a bounce starts X (finite, >= 0; default 1e-4) off its surface
@@ -82,6 +85,7 @@ const char *kUsage =
     "  --shadows 0|1 --seed S --face K   shadow rays, light-face choice\n"
     "  --dump-f32 path            raw fp32 framebuffer\n"
     "  --spp N                    N = n*n samples per pixel, n in 1..8\n"
+    "  --adaptive T               with --spp: refine only pixels whose contrast to a 4-neighbour exceeds T\n"
     "  --bounces N                up to N (0..16) bounces: mirror reflections weighted by ks\n"
     "  --bias X                   with --bounces: a bounce starts X off its surface (default 1e-4)\n"
     "  --refract                  with --bounces: transmissive materials (Tf / Ni) refract\n"
@@ -97,7 +101,8 @@ int main(int argc, char *argv[]) {
   float eye[3] = {0, 1, 3}, look[3] = {0, 1, 0}; // main.cpp:426
   int W = 1024, H = 768;                         // main.cpp:427
   int gpus = 1, shadows = 1, fixed_face = -1, spp = 0, bounces = -1;
-  float bias = 1e-4f;
+  float bias = 1e-4f, adaptive = 0.f;
+  bool have_adaptive = false;
   bool have_bias = false, refract = false, fresnel = false;
   unsigned long long seed = 0;
 
@@ -144,6 +149,17 @@ int main(int argc, char *argv[]) {
       arg++;
       continue;
     }
+    if (a == "--adaptive") {
+      if (!next) die("--adaptive needs T");
+      char *end = nullptr;
+      const float v = std::strtof(next, &end);
+      if (end == next || *end != '\0' || !(v >= 0.f) || !std::isfinite(v))
+        die(std::string("--adaptive must be a finite number >= 0, got ") + next);
+      adaptive = v;
+      have_adaptive = true;
+      arg++;
+      continue;
+    }
     if (a == "--bounces") {
       if (!next) die("--bounces needs N");
       char *end = nullptr;
@@ -179,6 +195,8 @@ int main(int argc, char *argv[]) {
   if (spp && (ispc || flat || gpus != 1)) die("--spp renders on one GPU and not with --ispc, --bvh or --bvh-tree");
   if (bounces >= 0 && (ispc || flat || gpus != 1))
     die("--bounces renders on one GPU and not with --ispc, --bvh or --bvh-tree");
+  if (have_adaptive && !spp) die("--adaptive needs --spp");
+  if (have_adaptive && bounces >= 0) die("--adaptive refines plain frames: not with --bounces");
   if (have_bias && bounces < 0) die("--bias needs --bounces");
   if (refract && fresnel) die("--refract and --fresnel exclude each other");
   if (refract && bounces < 0) die("--refract needs --bounces");
@@ -279,7 +297,10 @@ int main(int argc, char *argv[]) {
       check(esc_render_traced_ex(ctx, &cam, W, H, spp ? spp : 1, &so, &to, d_image, nullptr), "render");
     } else if (bounces >= 0)
       check(esc_render_traced(ctx, &cam, W, H, spp ? spp : 1, bounces, bias, &so, d_image, nullptr), "render");
-    else
+    else if (have_adaptive) {
+      const esc_adaptive_options ao = {spp, adaptive, 0, 0};
+      check(esc_render_adaptive(ctx, &cam, W, H, &so, &ao, d_image, nullptr, nullptr), "render");
+    } else
       check(esc_render_supersampled(ctx, &cam, W, H, spp, &so, d_image, nullptr), "render");
     check(esc_context_synchronize(ctx), "render");
     if (hipMemcpy(image.data(), d_image, image.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)

@@ -575,6 +575,51 @@ int esc_last_shade_stats(esc_context *ctx, esc_shade_stats *out);
 int esc_render_supersampled(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
                             const esc_render_options *opts, float *d_image, uint8_t *d_u8);
 
+/* ---- adaptive supersampling: refine only the pixels on an edge (rt_adaptive.hip, DESIGN.md section
+ * 3.16) ----
+ * An anti-aliased frame that pays the spp samples only where the 1-sample frame has contrast.  All
+ * comparisons are fp32:
+ *   1. B = the frame esc_render_rows writes for rows [0, H) with `opts`, bit for bit, on the frame
+ *      kernels (as a render call it touches camera state, lists and render counters the way
+ *      esc_render_rows does);
+ *   2. M[h,w] = 1 iff some 4-neighbour (h',w') inside the frame and some channel c has
+ *      !(fabsf(B[h,w,c] - B[h',w',c]) <= threshold): a NaN difference refines, both pixels of an edge
+ *      pair refine, and M is defined on the whole of B, never on pixels that were already refined;
+ *   3. a pixel with M = 1 takes the value esc_render_supersampled(spp) gives that pixel, bit for bit
+ *      (sample k = j*n + i at (i + 0.5f)/n - 0.5f, (j + 0.5f)/n - 0.5f, pixel id h*W + w, seed
+ *      opts.seed + k, acc = 0; acc += rgb_k in order; acc / float(spp));
+ *   4. every other pixel keeps B.
+ * d_image: W*H*3 floats; d_u8 (or NULL) the quantisation of the final image (main.cpp:676-682); d_mask
+ * (W*H bytes, or NULL) receives M.  spp == 1, or a threshold nothing exceeds, gives the frame itself, bit
+ * for bit.  Asynchronous on the context's stream: the masked pixels are listed and refined on the device,
+ * no host synchronisation happens inside the call.  The scratch is the context's and only grows: 1 byte
+ * per pixel for M when d_mask is NULL, plus 4 bytes per pixel of a band for the list; band_rows == 0
+ * keeps the list at or below 256 MB.  The image does not depend on band_rows.
+ * spp, W, H, cam, opts and alignment follow esc_render_supersampled; a negative, NaN or infinite
+ * threshold, reserved != 0 or band_rows < 0 is ESC_ERR_INVALID. */
+typedef struct esc_adaptive_options {
+  int32_t spp;       /* n*n, n in 1..8: samples of a refined pixel */
+  float threshold;   /* >= 0, finite */
+  int32_t band_rows; /* 0 = automatic; > 0: refine in bands of this many rows (memory knob) */
+  int32_t reserved;  /* 0 */
+} esc_adaptive_options;
+/* counts of the last esc_render_adaptive call (zero before the first) */
+typedef struct esc_adaptive_stats {
+  uint64_t pixels;         /* W * H */
+  uint64_t refined_pixels; /* pixels with M = 1 */
+  uint64_t samples;        /* refined_pixels * spp */
+  /* of the refinement rays, as esc_shade_stats counts them */
+  uint64_t hit_rays;
+  uint64_t shadow_rays;
+  uint64_t exact_rays;
+  uint64_t exact_tests;
+} esc_adaptive_stats;
+int esc_render_adaptive(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
+                        const esc_render_options *opts, const esc_adaptive_options *adaptive_opts,
+                        float *d_image, uint8_t *d_u8, uint8_t *d_mask);
+/* synchronises the context's stream */
+int esc_last_adaptive_stats(esc_context *ctx, esc_adaptive_stats *out);
+
 /* ---- mirror reflections: a fused on-device bounce loop (rt_trace.hip) ----
  * An extension beyond the reference (which casts no secondary rays), driven by the material's ks.
  * For one ray (o, d) with pixel id q = pixel_base + i (mod 2^32), max_depth = D and bias, all
