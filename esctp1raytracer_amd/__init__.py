@@ -189,6 +189,15 @@ class Scene:
                 "root": info.sph_root if w else info.tri_root,
                 "depth": info.sph_depth if w else info.tri_depth, "build_ms": info.build_ms}
 
+    def table(self, name):
+        """Host only (no GPU needed): one of the tables an upload of this scene computes, as the
+        bytes it uploads (numpy.uint8).  `name` is one of _capi.ESC_TABLE_NAMES: the staged records,
+        the computed tables (csrc/rt_device.h layouts), or "header" (esc_scene_table_header)."""
+        which = _capi.ESC_TABLE_NAMES.index(name)
+        out = np.zeros(check(self._lib.esc_scene_table(self._h, which, None, 0)), np.uint8)
+        check(self._lib.esc_scene_table(self._h, which, out.ctypes.data, out.size))
+        return out
+
     def flatten_ispc(self, sort_by_centroid_x=False):
         """flatten_scene_ispc (flatten_iscp.cpp:35-111) -> FlatScene."""
         return FlatScene(self, sort_by_centroid_x)

@@ -41,6 +41,12 @@ ESC_RENDER_NO_LIGHT_LISTS = 64
 ESC_RENDER_TWO_KERNELS = 128
 ESC_RENDER_BVH_HEURISTIC_PADS = 256
 ESC_RENDER_NO_COUNTERS = 512
+# ESC_TABLE_*: the index of a name is its value
+ESC_TABLE_NAMES = ("tri", "tri_n", "sph", "sph_mat", "mat", "transmit", "lights", "light_points",
+                   "sph2", "sph2_f", "sph2_ord", "sph2_f_ord", "tri2_f", "tri2_pf",
+                   "sg_sorted", "sg_grp", "sg_orig", "sg_sorted2", "sg_sorted2_f", "sg_grp2_f",
+                   "tg_sorted", "tg_grp", "tg_orig", "tg_sorted2_f", "tg_sorted2_pf", "tg_grp2_pf",
+                   "header")
 
 
 class EscError(RuntimeError):
@@ -197,6 +203,7 @@ SIGNATURES = {
     "esc_scene_build_accel": (C.c_int, [_P, _F, C.c_int32, C.POINTER(esc_accel_info),
                                         C.POINTER(esc_bvh_node), C.c_int64, _I32, C.c_int64, _F,
                                         C.c_int64]),
+    "esc_scene_table": (C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
     "esc_queue_schedule": (C.c_int, [C.c_int32, C.c_int32, _I32, C.c_int32]),
     "esc_tri_group_record": (C.c_int, [_F, C.c_int32, _F]),
     "esc_sphere_group_record": (C.c_int, [_F, C.c_int32, _F]),

@@ -15,6 +15,7 @@
 
 #include "../host/accel_build.h"
 #include "../host/scene.h"
+#include "../host/scene_tables.h"
 #include "rt_adaptive.h"
 #include "rt_device.h"
 #include "rt_query.h"
@@ -60,6 +61,9 @@ extern "C" int esc_launch_assemble(const void *gathered, void *frame, size_t ran
                                    hipStream_t stream);
 
 using esc::set_error;
+using esc::stage_flat;
+using esc::stage_scene;
+using esc::Staged;
 
 #define HIP_TRY(expr)                                                                      \
   do {                                                                                     \
@@ -190,179 +194,6 @@ struct esc_context {
 
 namespace {
 
-// host-side image of the HBM tables, filled by either staging front-end
-struct Staged {
-  std::vector<esc::DevTri> tri;
-  std::vector<esc::DevTriN> tri_n; // empty when no geometry has normals
-  std::vector<esc::DevSph> sph;
-  std::vector<int32_t> sph_mat;
-  std::vector<esc::DevMat> mat;
-  std::vector<float> transmit; // 4 per entry of mat: tf[3], ni
-  std::vector<esc::DevLight> lights;
-  std::vector<float> light_points; // xyz0
-  int n_geom = 0;
-};
-
-esc::DevMat dev_material(const esc::Material &m, bool has_normals) {
-  esc::DevMat d;
-  std::memset(&d, 0, sizeof(d));
-  std::memcpy(d.ka, m.ka, 12);
-  std::memcpy(d.kd, m.kd, 12);
-  std::memcpy(d.ks, m.ks, 12);
-  std::memcpy(d.ke, m.ke, 12);
-  d.Ns = m.Ns;
-  d.has_normals = has_normals ? 1 : 0;
-  d.spec_free = esc::material_spec_free(d.ks, d.Ns);
-  return d;
-}
-
-esc::DevTri dev_triangle(const float *v0, const float *v1, const float *v2, int geom) {
-  esc::DevTri t;
-  std::memset(&t, 0, sizeof(t));
-  for (int i = 0; i < 3; i++) {
-    t.v0[i] = v0[i];
-    t.e1[i] = v1[i] - v0[i]; // ray_triangle.h:14
-    t.e2[i] = v2[i] - v0[i]; // ray_triangle.h:15
-  }
-  t.geom = geom;
-  return t;
-}
-
-void push_light_point(Staged &s, const float *v) {
-  // main.cpp:753-754 with v0 = v1 = v2: P = v0 + ((v1-v0)*r1 + (v2-v0)*r2) = v0 + (+0)
-  s.light_points.push_back(v[0] + 0.0f);
-  s.light_points.push_back(v[1] + 0.0f);
-  s.light_points.push_back(v[2] + 0.0f);
-  s.light_points.push_back(0.0f);
-}
-
-void push_transmission(Staged &s, const esc::Transmission &t) {
-  s.transmit.insert(s.transmit.end(), t.tf, t.tf + 3);
-  s.transmit.push_back(t.ni);
-}
-
-int stage_scene(const esc_scene &scene, Staged &s) {
-  bool any_normals = false;
-  for (const auto &g : scene.geometry) any_normals |= !g.normals.empty();
-  s.n_geom = (int)scene.geometry.size();
-  for (size_t gi = 0; gi < scene.geometry.size(); gi++) { // main.cpp:179-180 order
-    const esc::Geometry &g = scene.geometry[gi];
-    const bool hn = !g.normals.empty();
-    s.mat.push_back(dev_material(g.object_material, hn));
-    push_transmission(s, g.transmission);
-    for (size_t f = 0; f < g.n_faces(); f++) {
-      const uint32_t *face = &g.face_index[3 * f];
-      s.tri.push_back(dev_triangle(&g.vertex[3 * face[0]], &g.vertex[3 * face[1]],
-                                   &g.vertex[3 * face[2]], (int)gi));
-      s.tri.back().pad[0] = (int32_t)f; // face index within the geometry: the ray queries' prim
-      if (any_normals) {
-        esc::DevTriN n;
-        std::memset(&n, 0, sizeof(n));
-        if (hn) {
-          std::memcpy(n.n0, &g.normals[3 * face[0]], 12);
-          std::memcpy(n.n1, &g.normals[3 * face[1]], 12);
-          std::memcpy(n.n2, &g.normals[3 * face[2]], 12);
-        }
-        s.tri_n.push_back(n);
-      }
-    }
-  }
-  for (size_t k = 0; k < scene.spheres.size(); k++) {
-    const esc::Sphere &sp = scene.spheres[k];
-    esc::DevSph d;
-    d.cx = sp.cx;
-    d.cy = sp.cy;
-    d.cz = sp.cz;
-    d.r2 = sp.r * sp.r;
-    s.sph.push_back(d);
-    s.sph_mat.push_back(s.n_geom + (int)k);
-    s.mat.push_back(dev_material(scene.sphere_materials[k], false));
-    push_transmission(s, k < scene.sphere_transmission.size() ? scene.sphere_transmission[k] : esc::Transmission());
-  }
-  for (size_t li : scene.light_sources) { // main.cpp:740-748
-    const esc::Geometry &g = scene.geometry[li];
-    if (g.n_faces() == 0) {
-      set_error("light geometry has no faces: light.vertex[faceID] (main.cpp:748) has nothing "
-                "to sample");
-      return ESC_ERR_INVALID;
-    }
-    if (g.n_faces() > g.n_vertices()) {
-      set_error("light geometry has more faces than vertices: light.vertex[faceID] "
-                "(main.cpp:748) would read out of range");
-      return ESC_ERR_INVALID;
-    }
-    esc::DevLight L;
-    L.first_point = (int)(s.light_points.size() / 4);
-    L.n_faces = (int)g.n_faces();
-    for (size_t k = 0; k < g.n_faces(); k++) push_light_point(s, &g.vertex[3 * k]);
-    s.lights.push_back(L);
-  }
-  return ESC_OK;
-}
-
-int stage_flat(int32_t nt, const ispc_triangle *tris, int32_t nl, const ispc_light *lights,
-               int32_t nlt, const ispc_triangle *ltris, Staged &s) {
-  int max_geom = -1;
-  bool any_normals = false;
-  for (int i = 0; i < nt; i++) {
-    if (tris[i].geom_id < 0) {
-      set_error("ispc_triangle.geom_id < 0");
-      return ESC_ERR_INVALID;
-    }
-    max_geom = std::max(max_geom, (int)tris[i].geom_id);
-    any_normals |= tris[i].has_normals != 0;
-  }
-  s.n_geom = max_geom + 1;
-  s.mat.resize((size_t)s.n_geom);
-  std::memset(s.mat.data(), 0, s.mat.size() * sizeof(esc::DevMat));
-  for (int g = 0; g < s.n_geom; g++) push_transmission(s, esc::Transmission()); // the seam carries none
-  for (int i = 0; i < nt; i++) {
-    const ispc_triangle &t = tris[i];
-    s.tri.push_back(dev_triangle(t.vertices[0], t.vertices[1], t.vertices[2], t.geom_id));
-    s.tri.back().pad[0] = i; // index in triangles[]: the ray queries' prim
-    esc::DevMat &m = s.mat[(size_t)t.geom_id]; // material is replicated per triangle
-    std::memcpy(m.ka, t.ka, 12);
-    std::memcpy(m.kd, t.kd, 12);
-    std::memcpy(m.ks, t.ks, 12);
-    std::memcpy(m.ke, t.ke, 12);
-    m.Ns = t.Ns;
-    m.has_normals = t.has_normals ? 1 : 0;
-    m.spec_free = esc::material_spec_free(m.ks, m.Ns);
-    if (any_normals) {
-      esc::DevTriN n;
-      std::memset(&n, 0, sizeof(n));
-      if (t.has_normals) {
-        std::memcpy(n.n0, t.normals[0], 12);
-        std::memcpy(n.n1, t.normals[1], 12);
-        std::memcpy(n.n2, t.normals[2], 12);
-      }
-      s.tri_n.push_back(n);
-    }
-  }
-  for (int li = 0; li < nl; li++) {
-    const ispc_light &L = lights[li];
-    esc::DevLight D;
-    D.first_point = (int)(s.light_points.size() / 4);
-    if (L.num_light_faces < 1 || !L.light_faces) {
-      // the face draw of main.cpp:743-748 is `% face count`; an empty light has no sample point
-      set_error("ispc_light.num_light_faces must be >= 1 and light_faces non-null");
-      return ESC_ERR_INVALID;
-    }
-    D.n_faces = L.num_light_faces;
-    // the scalar path's light.vertex[k], k < n_faces, is corner k%3 of light face k/3
-    for (int k = 0; k < L.num_light_faces; k++) {
-      const int fi = L.light_faces[k / 3];
-      if (fi < 0 || fi >= nlt) {
-        set_error("ispc_light.light_faces index out of range");
-        return ESC_ERR_INVALID;
-      }
-      push_light_point(s, ltris[fi].vertices[k % 3]);
-    }
-    s.lights.push_back(D);
-  }
-  return ESC_OK;
-}
-
 template <typename T> int upload_vec(T *&dptr, const std::vector<T> &h, hipStream_t st) {
   if (dptr) {
     HIP_TRY(hipFree(dptr));
@@ -372,6 +203,14 @@ template <typename T> int upload_vec(T *&dptr, const std::vector<T> &h, hipStrea
   HIP_TRY(hipMalloc((void **)&dptr, h.size() * sizeof(T)));
   HIP_TRY(hipMemcpyAsync(dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
   return ESC_OK;
+}
+
+// the tables the kernels only read are `const T *` in the parameter blocks; the context still owns them
+template <typename T> int upload_vec(const T *&dptr, const std::vector<T> &h, hipStream_t st) {
+  T *d = const_cast<T *>(dptr);
+  const int rc = upload_vec(d, h, st);
+  dptr = d;
+  return rc;
 }
 
 template <typename T> int alloc_dev(T *&dptr, size_t n) {
@@ -386,500 +225,48 @@ template <typename T> int alloc_dev(T *&dptr, size_t n) {
 
 int commit(esc_context *ctx, const Staged &s) {
   HIP_TRY(hipSetDevice(ctx->device));
-  // pair-interleaved copy of the sphere table (rt_device.h DevSphPair)
-  std::vector<esc::DevSphPair> sph2((s.sph.size() + 1) / 2);
-  for (size_t j = 0; j < sph2.size(); j++)
-    for (int h = 0; h < 2; h++) {
-      const size_t k = 2 * j + h;
-      const bool real = k < s.sph.size();
-      sph2[j].cx[h] = real ? s.sph[k].cx : 0.f;
-      sph2[j].cy[h] = real ? s.sph[k].cy : 0.f;
-      sph2[j].cz[h] = real ? s.sph[k].cz : 0.f;
-      sph2[j].r2[h] = real ? s.sph[k].r2 : -__builtin_huge_valf(); // cc = +inf: never hit
-    }
-  // filter form of the pair table for shadow rays (rt_brute.h, proof next to pair4_any_filter_pk):
-  // centres relative to g = middle of the box of sphere centres, km rounded UP from double
-  // g = middle of the box of everything (sphere centres, triangle corners, light points); rho_max
-  // = twice the 1-norm radius of that box around g: every primary hit point, hence every first
-  // shadow-ray origin, lies inside it; origins further out (quirk S3 can start a later light's ray
-  // beyond the scene) take the exact path
-  float g[3] = {0.f, 0.f, 0.f};
-  double rho = 0.0;
-  {
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    auto grow = [&](double x, double y, double z) {
-      const double c[3] = {x, y, z};
-      for (int a = 0; a < 3; a++) {
-        lo[a] = std::min(lo[a], c[a]);
-        hi[a] = std::max(hi[a], c[a]);
-      }
-    };
-    for (const auto &q : s.sph) {
-      const double r = std::sqrt(std::max(0.0, (double)q.r2));
-      grow(q.cx - r, q.cy - r, q.cz - r);
-      grow(q.cx + r, q.cy + r, q.cz + r);
-    }
-    for (const auto &t : s.tri) {
-      grow(t.v0[0], t.v0[1], t.v0[2]);
-      grow((double)t.v0[0] + t.e1[0], (double)t.v0[1] + t.e1[1], (double)t.v0[2] + t.e1[2]);
-      grow((double)t.v0[0] + t.e2[0], (double)t.v0[1] + t.e2[1], (double)t.v0[2] + t.e2[2]);
-    }
-    if (lo[0] <= hi[0]) {
-      for (int a = 0; a < 3; a++) {
-        g[a] = (float)(0.5 * (lo[a] + hi[a]));
-        rho += std::max(hi[a] - (double)g[a], (double)g[a] - lo[a]);
-      }
-      rho = 2.0 * rho + 1e-30;
-      // the box itself, grown by 5 % of its size and rounded outwards: the region the light lists'
-      // reach is computed for (rt_lists.h "Light lists"; every first shadow-ray origin is inside)
-      const double grow_by = 0.05 * ((hi[0] - lo[0]) + (hi[1] - lo[1]) + (hi[2] - lo[2])) + 1e-30;
-      for (int a = 0; a < 3; a++) {
-        ctx->scene_lo[a] = std::nextafterf((float)(lo[a] - grow_by), -__builtin_huge_valf());
-        ctx->scene_hi[a] = std::nextafterf((float)(hi[a] + grow_by), __builtin_huge_valf());
-      }
-    } else {
-      for (int a = 0; a < 3; a++) ctx->scene_lo[a] = ctx->scene_hi[a] = 0.f;
-    }
-  }
-  // filter form of the triangle table for shadow rays (rt_brute.h "Triangle FILTERS"), in double,
-  // margins rounded up
-  auto build_tri2f = [&](const std::vector<esc::DevTri> &src) {
-  std::vector<esc::DevTriPairF> tri2f((src.size() + 1) / 2);
-  for (size_t j = 0; j < tri2f.size(); j++)
-    for (int h = 0; h < 2; h++) {
-      esc::DevTriPairF &F = tri2f[j];
-      const size_t k = 2 * j + h;
-      float *f[15] = {&F.n1x[h], &F.n1y[h], &F.n1z[h], &F.e1x[h], &F.e1y[h], &F.e1z[h], &F.e2x[h],
-                      &F.e2y[h], &F.e2z[h], &F.k1x[h], &F.k1y[h], &F.k1z[h], &F.k2x[h], &F.k2y[h],
-                      &F.k2z[h]};
-      if (k >= src.size()) {
-        for (float *x : f) *x = 0.f;
-        F.M[h] = -1.f; // A = 0*0 + M < 0: never a candidate
-        continue;
-      }
-      const esc::DevTri &t = src[k];
-      const float v[3] = {(float)((double)t.v0[0] - g[0]), (float)((double)t.v0[1] - g[1]),
-                          (float)((double)t.v0[2] - g[2])};
-      const double e1[3] = {t.e1[0], t.e1[1], t.e1[2]}, e2[3] = {t.e2[0], t.e2[1], t.e2[2]},
-                   vd[3] = {v[0], v[1], v[2]};
-      auto cross = [](const double *a, const double *b, double *o) {
-        o[0] = a[1] * b[2] - a[2] * b[1];
-        o[1] = a[2] * b[0] - a[0] * b[2];
-        o[2] = a[0] * b[1] - a[1] * b[0];
-      };
-      double n1[3], k1[3], k2[3];
-      cross(e2, e1, n1);
-      cross(e1, vd, k1);
-      cross(e2, vd, k2);
-      for (int a = 0; a < 3; a++) {
-        *f[a] = (float)n1[a];
-        *f[3 + a] = t.e1[a];
-        *f[6 + a] = t.e2[a];
-        *f[9 + a] = (float)k1[a];
-        *f[12 + a] = (float)k2[a];
-      }
-      const double a1 = std::fabs(e1[0]) + std::fabs(e1[1]) + std::fabs(e1[2]);
-      const double a2 = std::fabs(e2[0]) + std::fabs(e2[1]) + std::fabs(e2[2]);
-      const double av = std::fabs(vd[0]) + std::fabs(vd[1]) + std::fabs(vd[2]);
-      const double p12 = a1 * a2;
-      const double M = 0x1p-17 * p12 * (p12 + (a1 + a2) * (av + rho)) + 0x1p-120;
-      float Mf = (float)M;
-      if ((double)Mf < M) Mf = std::nextafterf(Mf, __builtin_huge_valf());
-      F.M[h] = Mf;
-    }
-  return tri2f;
-  };
-  const std::vector<esc::DevTriPairF> tri2f = build_tri2f(s.tri);
-  std::vector<esc::DevSphPairF> sph2f(sph2.size());
-  for (size_t j = 0; j < sph2f.size(); j++)
-    for (int h = 0; h < 2; h++) {
-      const size_t k = 2 * j + h;
-      esc::DevSphPairF &F = sph2f[j];
-      if (k >= s.sph.size()) {
-        F.cx[h] = F.cy[h] = F.cz[h] = 0.f;
-        F.km[h] = -__builtin_huge_valf(); // q' = -inf: never a candidate
-        continue;
-      }
-      const float c[3] = {(float)((double)s.sph[k].cx - g[0]), (float)((double)s.sph[k].cy - g[1]),
-                          (float)((double)s.sph[k].cz - g[2])};
-      const double c2 = (double)c[0] * c[0] + (double)c[1] * c[1] + (double)c[2] * c[2];
-      const double r2 = (double)s.sph[k].r2;
-      const double km = r2 - c2 + 0x1p-16 * (c2 + std::fabs(r2)) + 0x1p-120;
-      float kf = (float)km;
-      if ((double)kf < km) kf = std::nextafterf(kf, __builtin_huge_valf());
-      if (kf != kf) kf = __builtin_huge_valf(); // non-finite input: "always a candidate", not the negative default NaN
-      F.cx[h] = c[0];
-      F.cy[h] = c[1];
-      F.cz[h] = c[2];
-      F.km[h] = kf;
-    }
-  // pre-filter form of the triangle table for shadow rays (rt_brute.h "Triangle pre-filter"):
-  // bounding sphere (G, R) in DevSphPairF form + the normal scaled by 1 / tau', in double
-  auto build_tri2pf = [&](const std::vector<esc::DevTri> &src) {
-  std::vector<esc::DevTriPairPF> tri2pf((src.size() + 1) / 2);
-  for (size_t j = 0; j < tri2pf.size(); j++)
-    for (int h = 0; h < 2; h++) {
-      esc::DevTriPairPF &F = tri2pf[j];
-      const size_t k = 2 * j + h;
-      F.cx[h] = F.cy[h] = F.cz[h] = 0.f;
-      F.gx[h] = F.gy[h] = F.gz[h] = F.pad[h] = 0.f;
-      F.km[h] = -__builtin_huge_valf(); // pad half: never a candidate, never "nearly parallel" ...
-      if (k >= src.size()) {
-        F.gx[h] = 4.f; // ... (|L . (4,4,4)| >= 4 / sqrt(3) > 1 for a unit L)
-        F.gy[h] = 4.f;
-        F.gz[h] = 4.f;
-        continue;
-      }
-      F.km[h] = __builtin_huge_valf(); // sliver: always a candidate (g'' = 0 too)
-      const esc::DevTri &t = src[k];
-      const double e1[3] = {t.e1[0], t.e1[1], t.e1[2]}, e2[3] = {t.e2[0], t.e2[1], t.e2[2]};
-      double G[3], s3[3], r0 = 0, r1 = 0, r2 = 0, l1 = 0, l2 = 0, a1 = 0, a2 = 0, av = 0;
-      for (int a = 0; a < 3; a++) {
-        s3[a] = (e1[a] + e2[a]) / 3.0;
-        G[a] = (double)t.v0[a] + s3[a];
-        r0 += s3[a] * s3[a];
-        r1 += (e1[a] - s3[a]) * (e1[a] - s3[a]);
-        r2 += (e2[a] - s3[a]) * (e2[a] - s3[a]);
-        l1 += e1[a] * e1[a];
-        l2 += e2[a] * e2[a];
-        a1 += std::fabs(e1[a]);
-        a2 += std::fabs(e2[a]);
-        av += std::fabs((double)(float)((double)t.v0[a] - g[a]));
-      }
-      const double rad = std::sqrt(std::max(r0, std::max(r1, r2)));
-      const double emax = std::sqrt(std::max(l1, l2));
-      if (!(rad > 0x1p-10 * emax)) continue;
-      const double u = 0x1p-24, at = rho + av, p12 = a1 * a2;
-      const double tau = 3.2 * u * (10.04 * at * a2 + 5.04 * at * a1 + 20.1 * p12) * emax / rad;
-      const double taup = (tau + 10.1 * u * p12) * 1.00001 + 0x1p-120;
-      const double R = 2.0 * rad + 8.0 * u * (at + a1 + a2);
-      const float c[3] = {(float)(G[0] - g[0]), (float)(G[1] - g[1]), (float)(G[2] - g[2])};
-      const double c2 = (double)c[0] * c[0] + (double)c[1] * c[1] + (double)c[2] * c[2];
-      const double R2 = R * R * 1.00001;
-      const double km = R2 - c2 + 0x1p-16 * (c2 + R2) + 0x1p-120;
-      float kf = (float)km;
-      if ((double)kf < km) kf = std::nextafterf(kf, __builtin_huge_valf());
-      if (kf != kf) kf = __builtin_huge_valf(); // (as above)
-      F.cx[h] = c[0];
-      F.cy[h] = c[1];
-      F.cz[h] = c[2];
-      F.km[h] = kf;
-      const double n1[3] = {e2[1] * e1[2] - e2[2] * e1[1], e2[2] * e1[0] - e2[0] * e1[2],
-                            e2[0] * e1[1] - e2[1] * e1[0]};
-      F.gx[h] = (float)(n1[0] / taup);
-      F.gy[h] = (float)(n1[1] / taup);
-      F.gz[h] = (float)(n1[2] / taup);
-    }
-  return tri2pf;
-  };
-  const std::vector<esc::DevTriPairPF> tri2pf = build_tri2pf(s.tri);
-  // the LAST light's sweep order (ESC_RENDER_INDEX_ORDER switches it off): spheres by decreasing
-  // solid angle r^2 / |c - P|^2 seen from its first sample point P.  Same records, permuted pair
-  // tables (exact + filter); from 256 spheres up.
-  std::vector<esc::DevSphPair> sph2o;
-  std::vector<esc::DevSphPairF> sph2fo;
-  if (!s.lights.empty() && s.sph.size() >= 256) {
-    const float *P = &s.light_points[4 * (size_t)s.lights.back().first_point];
-    std::vector<int> ord(s.sph.size());
-    std::vector<double> key(s.sph.size());
-    for (size_t k = 0; k < s.sph.size(); k++) {
-      ord[k] = (int)k;
-      const double dx = (double)s.sph[k].cx - P[0], dy = (double)s.sph[k].cy - P[1],
-                   dz = (double)s.sph[k].cz - P[2];
-      key[k] = (double)s.sph[k].r2 / std::max(dx * dx + dy * dy + dz * dz, 1e-300);
-    }
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return key[a] > key[b]; });
-    sph2o.resize(sph2.size());
-    sph2fo.resize(sph2f.size());
-    for (size_t pos = 0; pos < 2 * sph2.size(); pos++) {
-      const size_t j = pos >> 1;
-      const int h = (int)(pos & 1);
-      if (pos < ord.size()) {
-        const size_t k = (size_t)ord[pos];
-        sph2o[j].cx[h] = sph2[k >> 1].cx[k & 1];
-        sph2o[j].cy[h] = sph2[k >> 1].cy[k & 1];
-        sph2o[j].cz[h] = sph2[k >> 1].cz[k & 1];
-        sph2o[j].r2[h] = sph2[k >> 1].r2[k & 1];
-        sph2fo[j].cx[h] = sph2f[k >> 1].cx[k & 1];
-        sph2fo[j].cy[h] = sph2f[k >> 1].cy[k & 1];
-        sph2fo[j].cz[h] = sph2f[k >> 1].cz[k & 1];
-        sph2fo[j].km[h] = sph2f[k >> 1].km[k & 1];
-      } else { // the pad half of an odd count stays last
-        sph2o[j].cx[h] = sph2o[j].cy[h] = sph2o[j].cz[h] = 0.f;
-        sph2o[j].r2[h] = -__builtin_huge_valf();
-        sph2fo[j].cx[h] = sph2fo[j].cy[h] = sph2fo[j].cz[h] = 0.f;
-        sph2fo[j].km[h] = -__builtin_huge_valf();
-      }
-    }
-  }
-  // sphere groups of the primary pass (rt_device.h SphGroups): spatial order, runs of kSphGroup,
-  // padded to whole sweep steps
-  std::vector<esc::DevSph> sg_sorted;
-  std::vector<esc::DevSphGroup> sg_grp;
-  std::vector<esc::DevIdx4> sg_orig;
-  size_t sg_n_grp = 0, sg_n_sup = 0;
-  if ((int)s.sph.size() >= esc::kSphGroupMinSpheres) {
-    std::vector<int32_t> order;
-    constexpr size_t kBig = (size_t)esc::kSphGroup * esc::kSphSuper; // spheres per super-group
-    constexpr size_t kHuge = kBig * esc::kSphHyper;                  // ... per hyper-group
-    esc::group_order(s.sph, esc::kSphGroup, (int)kBig, (int)kHuge, order);
-    const size_t n_real = (s.sph.size() + esc::kSphGroup - 1) / esc::kSphGroup;
-    const size_t n_sup_real = (s.sph.size() + kBig - 1) / kBig;
-    const size_t n_hyp_real = (s.sph.size() + kHuge - 1) / kHuge;
-    const size_t n_hyp = (n_hyp_real + esc::kSphGroupStep - 1) / esc::kSphGroupStep * esc::kSphGroupStep;
-    const size_t n_sup = n_hyp * esc::kSphHyper;
-    const size_t n_grp = n_sup * esc::kSphSuper;
-    esc::DevSph pad_s;
-    pad_s.cx = pad_s.cy = pad_s.cz = 0.f;
-    pad_s.r2 = -__builtin_huge_valf();
-    sg_sorted.assign(n_grp * esc::kSphGroup, pad_s);
-    esc::DevSphGroup pad_g;
-    pad_g.cx = pad_g.cy = pad_g.cz = 0.f;
-    pad_g.rgeo = -1.f;
-    sg_grp.assign(n_grp + n_sup + n_hyp, pad_g); // groups, then super-groups, then hyper-groups
-    esc::DevIdx4 pad_i;
-    pad_i.v[0] = pad_i.v[1] = pad_i.v[2] = pad_i.v[3] = INT32_MAX / 2;
-    sg_orig.assign(n_grp * esc::kSphGroup / 4, pad_i);
-    for (size_t k = 0; k < order.size(); k++) {
-      sg_sorted[k] = s.sph[(size_t)order[k]];
-      sg_orig[k >> 2].v[k & 3] = order[k];
-    }
-    for (size_t j = 0; j < n_real; j++) {
-      const size_t first = j * esc::kSphGroup;
-      sg_grp[j] = esc::group_bounds(s.sph, order.data() + first,
-                                    (int)std::min((size_t)esc::kSphGroup, order.size() - first));
-    }
-    for (size_t j = 0; j < n_sup_real; j++) {
-      const size_t first = j * kBig;
-      sg_grp[n_grp + j] =
-          esc::group_bounds(s.sph, order.data() + first, (int)std::min(kBig, order.size() - first));
-    }
-    for (size_t j = 0; j < n_hyp_real; j++) {
-      const size_t first = j * kHuge;
-      sg_grp[n_grp + n_sup + j] =
-          esc::group_bounds(s.sph, order.data() + first, (int)std::min(kHuge, order.size() - first));
-    }
-    sg_n_grp = n_grp;
-    sg_n_sup = n_sup;
-  }
-  // ... and the same groups for shadow rays: pair tables relative to g
-  std::vector<esc::DevSphPair> sg_sorted2(sg_sorted.size() / 2);
-  std::vector<esc::DevSphPairF> sg_sorted2f(sg_sorted.size() / 2), sg_grp2f(sg_grp.size() / 2);
-  {
-    auto filter_half = [&](esc::DevSphPairF &F, int h, double cx, double cy, double cz, double r2) {
-      const float c[3] = {(float)(cx - g[0]), (float)(cy - g[1]), (float)(cz - g[2])};
-      const double c2 = (double)c[0] * c[0] + (double)c[1] * c[1] + (double)c[2] * c[2];
-      const double km = r2 - c2 + 0x1p-16 * (c2 + std::fabs(r2)) + 0x1p-120;
-      float kf = (float)km;
-      if ((double)kf < km) kf = std::nextafterf(kf, __builtin_huge_valf());
-      F.cx[h] = c[0];
-      F.cy[h] = c[1];
-      F.cz[h] = c[2];
-      // a non-finite centre or radius gives km = NaN, and the x86 default NaN is NEGATIVE: read as
-      // an int32 it would say "never a candidate"; +inf says "always one" (the exact code decides)
-      if (kf != kf) kf = __builtin_huge_valf();
-      F.km[h] = kf;
-    };
-    for (size_t k = 0; k < sg_sorted.size(); k++) {
-      const esc::DevSph &q = sg_sorted[k];
-      const size_t j = k >> 1;
-      const int h = (int)(k & 1);
-      sg_sorted2[j].cx[h] = q.cx;
-      sg_sorted2[j].cy[h] = q.cy;
-      sg_sorted2[j].cz[h] = q.cz;
-      sg_sorted2[j].r2[h] = q.r2; // pad: -inf, never hit
-      if (q.r2 == -__builtin_huge_valf()) {
-        sg_sorted2f[j].cx[h] = sg_sorted2f[j].cy[h] = sg_sorted2f[j].cz[h] = 0.f;
-        sg_sorted2f[j].km[h] = -__builtin_huge_valf();
-      } else {
-        filter_half(sg_sorted2f[j], h, q.cx, q.cy, q.cz, q.r2);
-      }
-    }
-    for (size_t k = 0; k < sg_grp.size(); k++) {
-      const esc::DevSphGroup &G = sg_grp[k];
-      const size_t j = k >> 1;
-      const int h = (int)(k & 1);
-      if (G.rgeo < 0.f) {
-        sg_grp2f[j].cx[h] = sg_grp2f[j].cy[h] = sg_grp2f[j].cz[h] = 0.f;
-        sg_grp2f[j].km[h] = -__builtin_huge_valf();
-        continue;
-      }
-      const double dx = (double)G.cx - g[0], dy = (double)G.cy - g[1], dz = (double)G.cz - g[2];
-      const double R = (double)G.rgeo +
-                       0x1.6p-10 * (rho + std::sqrt(dx * dx + dy * dy + dz * dz) + (double)G.rgeo) + 0x1p-60;
-      filter_half(sg_grp2f[j], h, G.cx, G.cy, G.cz, R * R * 1.00001);
-    }
-  }
-  // triangle groups (rt_device.h TriGroups): spatial order, groups of 8, super-groups of 8 groups,
-  // padded to whole sweep steps; the shadow forms of the sorted triangles and of the groups
-  std::vector<esc::DevTri> tg_sorted;
-  std::vector<esc::DevTriGroup> tg_grp;
-  std::vector<esc::DevIdx4> tg_orig;
-  std::vector<esc::DevTriPairF> tg_sorted2f;
-  std::vector<esc::DevTriPairPF> tg_sorted2pf, tg_grp2pf;
-  size_t tg_n_grp = 0, tg_n_sup = 0;
-  if ((int)s.tri.size() >= esc::kTriGroupMinTris) {
-    constexpr size_t kBig = (size_t)esc::kTriGroup * esc::kTriSuper;
-    constexpr size_t kHuge = kBig * esc::kTriHyper;
-    std::vector<int32_t> order;
-    esc::group_order(s.tri, esc::kTriGroup, (int)kBig, (int)kHuge, order);
-    const size_t n_real = (s.tri.size() + esc::kTriGroup - 1) / esc::kTriGroup;
-    const size_t n_sup_real = (s.tri.size() + kBig - 1) / kBig;
-    const size_t n_hyp_real = (s.tri.size() + kHuge - 1) / kHuge;
-    const size_t n_hyp = (n_hyp_real + esc::kTriGroupStep - 1) / esc::kTriGroupStep * esc::kTriGroupStep;
-    const size_t n_sup = n_hyp * esc::kTriHyper;
-    const size_t n_grp = n_sup * esc::kTriSuper;
-    esc::DevTri pad_t;
-    std::memset(&pad_t, 0, sizeof(pad_t));
-    tg_sorted.assign(n_grp * esc::kTriGroup, pad_t);
-    esc::DevTriGroup pad_g;
-    std::memset(&pad_g, 0, sizeof(pad_g));
-    pad_g.rgeo = -1.f;
-    pad_g.slack = 1.f;
-    tg_grp.assign(n_grp + n_sup + n_hyp, pad_g);
-    // shadow rays take the plain trade-off (slack 1) at every level: their cones are static, the
-    // sine term dominates them and a thinner tau band buys nothing, while the larger radii cost
-    std::vector<esc::DevTriGroup> tg_grp1(tg_grp.size(), pad_g);
-    esc::DevIdx4 pad_i;
-    pad_i.v[0] = pad_i.v[1] = pad_i.v[2] = pad_i.v[3] = INT32_MAX / 2;
-    tg_orig.assign(n_grp * esc::kTriGroup / 4, pad_i);
-    for (size_t k = 0; k < order.size(); k++) {
-      tg_sorted[k] = s.tri[(size_t)order[k]];
-      tg_orig[k >> 2].v[k & 3] = order[k];
-    }
-    for (size_t j = 0; j < n_real; j++) {
-      const size_t first = j * esc::kTriGroup;
-      tg_grp[j] = esc::tri_group_bounds(s.tri, order.data() + first,
-                                        (int)std::min((size_t)esc::kTriGroup, order.size() - first),
-                                        esc::kTriSlackGroup);
-      tg_grp1[j] = esc::tri_group_bounds(s.tri, order.data() + first,
-                                         (int)std::min((size_t)esc::kTriGroup, order.size() - first));
-    }
-    for (size_t j = 0; j < n_sup_real; j++) {
-      const size_t first = j * kBig;
-      tg_grp[n_grp + j] =
-          esc::tri_group_bounds(s.tri, order.data() + first, (int)std::min(kBig, order.size() - first),
-                                esc::kTriSlackSuper);
-      tg_grp1[n_grp + j] =
-          esc::tri_group_bounds(s.tri, order.data() + first, (int)std::min(kBig, order.size() - first));
-    }
-    for (size_t j = 0; j < n_hyp_real; j++) {
-      const size_t first = j * kHuge;
-      tg_grp[n_grp + n_sup + j] =
-          esc::tri_group_bounds(s.tri, order.data() + first, (int)std::min(kHuge, order.size() - first),
-                                esc::kTriSlackHyper);
-      tg_grp1[n_grp + n_sup + j] =
-          esc::tri_group_bounds(s.tri, order.data() + first, (int)std::min(kHuge, order.size() - first));
-    }
-    tg_n_grp = n_grp;
-    tg_n_sup = n_sup;
-    tg_sorted2f = build_tri2f(tg_sorted);
-    tg_sorted2pf = build_tri2pf(tg_sorted);
-    tg_grp2pf.resize(tg_grp.size() / 2);
-    for (size_t k = 0; k < tg_grp1.size(); k++) {
-      const esc::DevTriGroup &G = tg_grp1[k];
-      esc::DevTriPairPF &F = tg_grp2pf[k >> 1];
-      const int h = (int)(k & 1);
-      F.cx[h] = F.cy[h] = F.cz[h] = 0.f;
-      F.gx[h] = F.gy[h] = F.gz[h] = F.pad[h] = 0.f;
-      if (G.rgeo < 0.f) { // pad group: never a candidate, never "nearly parallel"
-        F.km[h] = -__builtin_huge_valf();
-        F.gx[h] = F.gy[h] = F.gz[h] = 0x1p60f;
-        continue;
-      }
-      F.km[h] = __builtin_huge_valf(); // always open unless the bounds below are usable
-      if (G.always != 0.f) continue;
-      const float c[3] = {(float)((double)G.cx - g[0]), (float)((double)G.cy - g[1]),
-                          (float)((double)G.cz - g[2])};
-      const double c1 = std::fabs((double)G.cx - g[0]) + std::fabs((double)G.cy - g[1]) +
-                        std::fabs((double)G.cz - g[2]);
-      const double at = rho + c1 + (double)G.rext; // >= |O - v0_t|_1 for every member and ray in range
-      const double kappa = ((double)G.smax + (double)G.b0 + (double)G.b1 * at + 0x1p-20) * 1.0001;
-      if (!(kappa < 1.0)) continue;
-      const double R = (double)G.rgeo + 0x1p-21 * at + 0x1p-60;
-      const double c2 = (double)c[0] * c[0] + (double)c[1] * c[1] + (double)c[2] * c[2];
-      const double R2 = R * R * 1.00001;
-      const double km = R2 - c2 + 0x1p-16 * (c2 + R2) + 0x1p-120;
-      if (!std::isfinite(km)) continue;
-      float kf = (float)km;
-      if ((double)kf < km) kf = std::nextafterf(kf, __builtin_huge_valf());
-      F.cx[h] = c[0];
-      F.cy[h] = c[1];
-      F.cz[h] = c[2];
-      F.km[h] = kf;
-      F.gx[h] = (float)((double)G.ax / kappa);
-      F.gy[h] = (float)((double)G.ay / kappa);
-      F.gz[h] = (float)((double)G.az / kappa);
-    }
-  }
+  esc::SceneTables t;
+  esc::build_scene_tables(s, t);
+  std::memcpy(ctx->scene_lo, t.scene_lo, sizeof(t.scene_lo));
+  std::memcpy(ctx->scene_hi, t.scene_hi, sizeof(t.scene_hi));
   HIP_TRY(hipStreamSynchronize(ctx->stream)); // nothing in flight may still read old tables
   int rc;
-  {
-    esc::DevTri *d_t = const_cast<esc::DevTri *>(ctx->tg.sorted);
-    esc::DevIdx4 *d_o = const_cast<esc::DevIdx4 *>(ctx->tg.orig);
-    esc::DevTriGroup *d_g = const_cast<esc::DevTriGroup *>(ctx->tg.grp);
-    esc::DevTriPairPF *d_s2pf = const_cast<esc::DevTriPairPF *>(ctx->tg.sorted2_pf);
-    esc::DevTriPairF *d_s2f = const_cast<esc::DevTriPairF *>(ctx->tg.sorted2_f);
-    esc::DevTriPairPF *d_g2pf = const_cast<esc::DevTriPairPF *>(ctx->tg.grp2_pf);
-    if ((rc = upload_vec(d_t, tg_sorted, ctx->stream))) return rc;
-    if ((rc = upload_vec(d_o, tg_orig, ctx->stream))) return rc;
-    if ((rc = upload_vec(d_g, tg_grp, ctx->stream))) return rc;
-    if ((rc = upload_vec(d_s2pf, tg_sorted2pf, ctx->stream))) return rc;
-    if ((rc = upload_vec(d_s2f, tg_sorted2f, ctx->stream))) return rc;
-    if ((rc = upload_vec(d_g2pf, tg_grp2pf, ctx->stream))) return rc;
-    ctx->tg.sorted = d_t;
-    ctx->tg.orig = d_o;
-    ctx->tg.grp = d_g;
-    ctx->tg.sorted2_pf = d_s2pf;
-    ctx->tg.sorted2_f = d_s2f;
-    ctx->tg.grp2_pf = d_g2pf;
-    if ((rc = alloc_dev(ctx->tg.sorted_p, tg_sorted.size()))) return rc;
-    if ((rc = alloc_dev(ctx->tg.sorted_f, tg_sorted.size()))) return rc;
-    if ((rc = alloc_dev(ctx->tg.sorted_pf, tg_sorted.size()))) return rc;
-    if ((rc = alloc_dev(ctx->tg.grp_pf, tg_grp.size()))) return rc;
-    if ((rc = alloc_dev(ctx->tg.esc, 3 * tg_grp.size()))) return rc; // three chains (rt_device.h)
-    ctx->tg.n_grp = (int32_t)tg_n_grp;
-    ctx->tg.n_sup = (int32_t)tg_n_sup;
-    ctx->tg.n_hyp = (int32_t)(tg_grp.size() - tg_n_grp - tg_n_sup);
-  }
-  {
-    esc::DevSphPair *d_s2 = const_cast<esc::DevSphPair *>(ctx->sg.sorted2);
-    esc::DevSphPairF *d_s2f = const_cast<esc::DevSphPairF *>(ctx->sg.sorted2_f);
-    esc::DevSphPairF *d_g2f = const_cast<esc::DevSphPairF *>(ctx->sg.grp2_f);
-    if ((rc = upload_vec(d_s2, sg_sorted2, ctx->stream))) return rc;
-    if ((rc = upload_vec(d_s2f, sg_sorted2f, ctx->stream))) return rc;
-    if ((rc = upload_vec(d_g2f, sg_grp2f, ctx->stream))) return rc;
-    ctx->sg.sorted2 = d_s2;
-    ctx->sg.sorted2_f = d_s2f;
-    ctx->sg.grp2_f = d_g2f;
-  }
-  {
-    esc::DevSph *d_sorted = const_cast<esc::DevSph *>(ctx->sg.sorted);
-    esc::DevSphGroup *d_grp = const_cast<esc::DevSphGroup *>(ctx->sg.grp);
-    esc::DevIdx4 *d_orig = const_cast<esc::DevIdx4 *>(ctx->sg.orig);
-    if ((rc = upload_vec(d_sorted, sg_sorted, ctx->stream))) return rc;
-    if ((rc = upload_vec(d_grp, sg_grp, ctx->stream))) return rc;
-    if ((rc = upload_vec(d_orig, sg_orig, ctx->stream))) return rc;
-    ctx->sg.sorted = d_sorted;
-    ctx->sg.grp = d_grp;
-    ctx->sg.orig = d_orig;
-    if ((rc = alloc_dev(ctx->sg.sorted_p, sg_sorted.size()))) return rc;
-    if ((rc = alloc_dev(ctx->sg.sorted_f, sg_sorted.size()))) return rc;
-    if ((rc = alloc_dev(ctx->sg.grp_f, sg_grp.size()))) return rc;
-    ctx->sg.n_grp = (int32_t)sg_n_grp;
-    ctx->sg.n_sup = (int32_t)sg_n_sup;
-    ctx->sg.n_hyp = (int32_t)(sg_grp.size() - sg_n_grp - sg_n_sup);
-  }
-  if ((rc = upload_vec(ctx->d_sph2_ord, sph2o, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_sph2_f_ord, sph2fo, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_sph2_f, sph2f, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->tg.sorted, t.tg_sorted, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->tg.orig, t.tg_orig, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->tg.grp, t.tg_grp, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->tg.sorted2_pf, t.tg_sorted2_pf, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->tg.sorted2_f, t.tg_sorted2_f, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->tg.grp2_pf, t.tg_grp2_pf, ctx->stream))) return rc;
+  if ((rc = alloc_dev(ctx->tg.sorted_p, t.tg_sorted.size()))) return rc;
+  if ((rc = alloc_dev(ctx->tg.sorted_f, t.tg_sorted.size()))) return rc;
+  if ((rc = alloc_dev(ctx->tg.sorted_pf, t.tg_sorted.size()))) return rc;
+  if ((rc = alloc_dev(ctx->tg.grp_pf, t.tg_grp.size()))) return rc;
+  if ((rc = alloc_dev(ctx->tg.esc, 3 * t.tg_grp.size()))) return rc; // three chains (rt_device.h)
+  ctx->tg.n_grp = t.tg_n_grp;
+  ctx->tg.n_sup = t.tg_n_sup;
+  ctx->tg.n_hyp = t.tg_n_hyp;
+  if ((rc = upload_vec(ctx->sg.sorted2, t.sg_sorted2, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->sg.sorted2_f, t.sg_sorted2_f, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->sg.grp2_f, t.sg_grp2_f, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->sg.sorted, t.sg_sorted, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->sg.grp, t.sg_grp, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->sg.orig, t.sg_orig, ctx->stream))) return rc;
+  if ((rc = alloc_dev(ctx->sg.sorted_p, t.sg_sorted.size()))) return rc;
+  if ((rc = alloc_dev(ctx->sg.sorted_f, t.sg_sorted.size()))) return rc;
+  if ((rc = alloc_dev(ctx->sg.grp_f, t.sg_grp.size()))) return rc;
+  ctx->sg.n_grp = t.sg_n_grp;
+  ctx->sg.n_sup = t.sg_n_sup;
+  ctx->sg.n_hyp = t.sg_n_hyp;
+  if ((rc = upload_vec(ctx->d_sph2_ord, t.sph2_ord, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->d_sph2_f_ord, t.sph2_f_ord, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->d_sph2_f, t.sph2_f, ctx->stream))) return rc;
   if ((rc = alloc_dev(ctx->d_sph_f, s.sph.size()))) return rc;
-  if ((rc = upload_vec(ctx->d_tri2_f, tri2f, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->d_tri2_f, t.tri2_f, ctx->stream))) return rc;
   if ((rc = alloc_dev(ctx->d_tri_f, s.tri.size()))) return rc;
   if ((rc = alloc_dev(ctx->d_tri_pf, s.tri.size()))) return rc;
-  if ((rc = upload_vec(ctx->d_tri2_pf, tri2pf, ctx->stream))) return rc;
-  std::memcpy(ctx->shadow_center, g, sizeof(g));
-  ctx->shadow_rho_max = (float)rho;
+  if ((rc = upload_vec(ctx->d_tri2_pf, t.tri2_pf, ctx->stream))) return rc;
+  std::memcpy(ctx->shadow_center, t.g, sizeof(t.g));
+  ctx->shadow_rho_max = t.rho_max;
   if ((rc = upload_vec(ctx->d_tri, s.tri, ctx->stream))) return rc;
   if ((rc = upload_vec(ctx->d_tri_n, s.tri_n, ctx->stream))) return rc;
   if ((rc = alloc_dev(ctx->d_tri_face, s.tri.size()))) return rc;
@@ -891,7 +278,7 @@ int commit(esc_context *ctx, const Staged &s) {
     }
   }
   if ((rc = upload_vec(ctx->d_sph, s.sph, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_sph2, sph2, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->d_sph2, t.sph2, ctx->stream))) return rc;
   if ((rc = upload_vec(ctx->d_sph_mat, s.sph_mat, ctx->stream))) return rc;
   if ((rc = upload_vec(ctx->d_mat, s.mat, ctx->stream))) return rc;
   if ((rc = upload_vec(ctx->d_transmit, s.transmit, ctx->stream))) return rc;
@@ -904,15 +291,8 @@ int commit(esc_context *ctx, const Staged &s) {
   ctx->n_sph = (int)s.sph.size();
   ctx->n_lights = (int)s.lights.size();
   ctx->n_geom = s.n_geom;
-  ctx->any_transmissive = false;
-  for (size_t i = 0; i + 3 < s.transmit.size(); i += 4) { // the kernel's test (rt_transmit.h)
-    const float *t = &s.transmit[i];
-    ctx->any_transmissive |= (t[0] > 0.f || t[1] > 0.f || t[2] > 0.f) && t[3] > 0.f;
-  }
-  ctx->min_light_faces = 0;
-  for (size_t i = 0; i < s.lights.size(); i++)
-    ctx->min_light_faces = (i == 0) ? s.lights[i].n_faces
-                                    : std::min(ctx->min_light_faces, (int)s.lights[i].n_faces);
+  ctx->any_transmissive = t.any_transmissive;
+  ctx->min_light_faces = t.min_light_faces;
   ctx->have_scene = true;
   ctx->epoch++;
   ctx->prepared = false;
@@ -1211,6 +591,38 @@ int esc_scene_build_accel(const esc_scene *scene, const float origin[3], int32_t
         std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   return ESC_OK;
+}
+
+int64_t esc_scene_table(const esc_scene *scene, int32_t which, void *out, int64_t capacity) {
+  if (!scene || which < 0 || which >= ESC_TABLE_COUNT || capacity < 0) {
+    set_error("esc_scene_table: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  Staged s;
+  int rc = stage_scene(*scene, s);
+  if (rc) return rc;
+  esc::SceneTables t;
+  esc::build_scene_tables(s, t);
+  esc_scene_table_header hdr;
+  std::memset(&hdr, 0, sizeof(hdr));
+  std::memcpy(hdr.g, t.g, sizeof(hdr.g));
+  hdr.rho_max = t.rho_max;
+  std::memcpy(hdr.scene_lo, t.scene_lo, sizeof(hdr.scene_lo));
+  std::memcpy(hdr.scene_hi, t.scene_hi, sizeof(hdr.scene_hi));
+  const int32_t counts[8] = {t.sg_n_grp, t.sg_n_sup, t.sg_n_hyp, t.tg_n_grp, t.tg_n_sup, t.tg_n_hyp,
+                             t.any_transmissive ? 1 : 0, t.min_light_faces};
+  std::memcpy(&hdr.sg_n_grp, counts, sizeof(counts));
+  auto bytes = [](const auto &v) { return std::make_pair((const void *)v.data(), v.size() * sizeof(v[0])); };
+  const std::pair<const void *, size_t> tables[ESC_TABLE_COUNT] = {
+      bytes(s.tri), bytes(s.tri_n), bytes(s.sph), bytes(s.sph_mat), bytes(s.mat), bytes(s.transmit),
+      bytes(s.lights), bytes(s.light_points), bytes(t.sph2), bytes(t.sph2_f), bytes(t.sph2_ord),
+      bytes(t.sph2_f_ord), bytes(t.tri2_f), bytes(t.tri2_pf), bytes(t.sg_sorted), bytes(t.sg_grp),
+      bytes(t.sg_orig), bytes(t.sg_sorted2), bytes(t.sg_sorted2_f), bytes(t.sg_grp2_f),
+      bytes(t.tg_sorted), bytes(t.tg_grp), bytes(t.tg_orig), bytes(t.tg_sorted2_f),
+      bytes(t.tg_sorted2_pf), bytes(t.tg_grp2_pf), {&hdr, sizeof(hdr)}};
+  const auto &tab = tables[which];
+  if (out && tab.second && capacity >= (int64_t)tab.second) std::memcpy(out, tab.first, tab.second);
+  return (int64_t)tab.second;
 }
 
 int esc_check_flat(int32_t num_triangles, const ispc_triangle *triangles, int32_t num_lights,

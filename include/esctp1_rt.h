@@ -425,6 +425,55 @@ int esc_scene_build_accel(const esc_scene *scene, const float origin[3], int32_t
                           int32_t *order, int64_t order_cap, float *prim_boxes,
                           int64_t prim_boxes_cap);
 
+/* The per-scene tables of a scene upload, in the record layouts of csrc/rt_device.h: first the
+ * staged scene, then what the host computes from it for the brute-force kernels (pair tables, the
+ * shadow filters' forms, the last light's sweep order, sphere and triangle groups: empty where the
+ * scene is below that table's threshold), then one esc_scene_table_header. */
+enum {
+  ESC_TABLE_TRI = 0,      /* DevTri */
+  ESC_TABLE_TRI_N,        /* DevTriN; empty when no geometry has normals */
+  ESC_TABLE_SPH,          /* DevSph */
+  ESC_TABLE_SPH_MAT,      /* int32 material index per sphere */
+  ESC_TABLE_MAT,          /* DevMat: geometries, then spheres */
+  ESC_TABLE_TRANSMIT,     /* 4 floats per material: tf[3], ni */
+  ESC_TABLE_LIGHTS,       /* DevLight */
+  ESC_TABLE_LIGHT_POINTS, /* 4 floats per sample point: xyz0 */
+  ESC_TABLE_SPH2,         /* DevSphPair */
+  ESC_TABLE_SPH2_F,       /* DevSphPairF */
+  ESC_TABLE_SPH2_ORD,     /* DevSphPair, the last light's sweep order */
+  ESC_TABLE_SPH2_F_ORD,   /* DevSphPairF, same order */
+  ESC_TABLE_TRI2_F,       /* DevTriPairF */
+  ESC_TABLE_TRI2_PF,      /* DevTriPairPF */
+  ESC_TABLE_SG_SORTED,    /* SphGroups: DevSph */
+  ESC_TABLE_SG_GRP,       /* DevSphGroup: groups, super-groups, hyper-groups */
+  ESC_TABLE_SG_ORIG,      /* DevIdx4 */
+  ESC_TABLE_SG_SORTED2,   /* DevSphPair */
+  ESC_TABLE_SG_SORTED2_F, /* DevSphPairF */
+  ESC_TABLE_SG_GRP2_F,    /* DevSphPairF */
+  ESC_TABLE_TG_SORTED,    /* TriGroups: DevTri */
+  ESC_TABLE_TG_GRP,       /* DevTriGroup: groups, super-groups, hyper-groups */
+  ESC_TABLE_TG_ORIG,      /* DevIdx4 */
+  ESC_TABLE_TG_SORTED2_F, /* DevTriPairF */
+  ESC_TABLE_TG_SORTED2_PF, /* DevTriPairPF */
+  ESC_TABLE_TG_GRP2_PF,   /* DevTriPairPF */
+  ESC_TABLE_HEADER,       /* esc_scene_table_header */
+  ESC_TABLE_COUNT
+};
+typedef struct {     /* 72 bytes */
+  float g[3];        /* the scene point the shadow filters work around (middle of the scene box) */
+  float rho_max;     /* shadow-ray origins further than this (1-norm) from g take the exact path */
+  float scene_lo[3]; /* the scene box grown by 5 %, rounded outwards (light lists) */
+  float scene_hi[3];
+  int32_t sg_n_grp, sg_n_sup, sg_n_hyp; /* sphere groups, super-groups, hyper-groups (pads included) */
+  int32_t tg_n_grp, tg_n_sup, tg_n_hyp; /* the same for triangles */
+  int32_t any_transmissive;             /* 1 when some material has tf > 0 and ni > 0 */
+  int32_t min_light_faces;              /* smallest face count among the lights; 0 without lights */
+} esc_scene_table_header;
+/* Host only (no GPU), for inspection and tests: table `which` (ESC_TABLE_*) of the tables
+ * esc_upload_scene computes for this scene, as the bytes it uploads.  Returns the table's size in
+ * bytes (copied when capacity suffices; out may be NULL to ask for the size) or a negative error. */
+int64_t esc_scene_table(const esc_scene *scene, int32_t which, void *out, int64_t capacity);
+
 /* Host only: the segments the queue form of the shading pass cuts occlusion()'s primitive list
  * into (main.cpp:314-329 order: triangles, then spheres).  segments receives 4 ints per segment:
  * first triangle, triangle count, first sphere PAIR record, pair-record count (either count may

@@ -32,6 +32,55 @@ def unit(v):
     return (v / n).astype(f32)
 
 
+# ------------------------------------------------------------------ the library's own tables
+# Each test below that restates the host side of a shadow filter (build_scene_tables in
+# host/scene_tables.cpp, what an upload computes) also puts N_CROSS of its own primitives into a Scene
+# and compares the restatement with the bytes of Scene.table (host only, no GPU): bit for bit.
+N_CROSS = 300
+
+
+def _scene_box(lo, hi):
+    """the scene point g = fl(middle of the scene box) and rho_max = twice the box's 1-norm radius
+    around g (+ tiny), from the box corners in double"""
+    g = (0.5 * (lo + hi)).astype(f32)
+    rho = 2.0 * np.maximum(hi - g, g - lo).sum() + 1e-30
+    return g, rho
+
+
+def _triangle_box(v0, e1, e2):
+    """the box of the corners v0, v0 + e1, v0 + e2, the sums taken in double as the library takes them"""
+    v0d = v0.astype(np.float64)
+    pts = np.concatenate([v0d, v0d + e1, v0d + e2])
+    return pts.min(axis=0), pts.max(axis=0)
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a, f32).view(np.uint32), np.ascontiguousarray(b, f32).view(np.uint32))
+
+
+def _pair_records(table, floats, n):
+    """a two-per-record table (field-interleaved halves) as one row of `floats` fields per primitive"""
+    return table.view(f32).reshape(-1, floats, 2).transpose(0, 2, 1).reshape(-1, floats)[:n]
+
+
+def _library_header(sc):
+    h = sc.table("header")[:16].view(f32)
+    return h[:3], h[3]
+
+
+def _triangle_scene(v0, e1, e2):
+    """a Scene of the triangles (v0, fl(v0 + e1), fl(v0 + e2)) and their records as staging takes them:
+    e = fl(v - v0), which need not be the e the corner was made from"""
+    import esctp1raytracer_amd as esc
+    v1, v2 = f32(v0 + e1), f32(v0 + e2)
+    sc = esc.Scene()
+    mat = np.zeros(13, f32)
+    mat[3:6] = 0.5  # kd; ke = 0: not a light
+    sc.add_geometry(np.stack([v0, v1, v2], axis=1).reshape(-1, 3),
+                    np.arange(3 * len(v0), dtype=np.uint32).reshape(-1, 3), mat)
+    return sc, f32(v1 - v0), f32(v2 - v0)
+
+
 def grazing_rays(rng, o, c, r, n):
     """n unit directions from o that pass the sphere (c, r) at (1 + delta) r, |delta| from 1e-7
     to 1e-2, both signs: half would hit, half would miss, all by a hair."""
@@ -95,9 +144,34 @@ def test_primary_filter_never_rejects_a_reference_candidate(scale):
     assert scaled(unit(rng.normal(size=(n, 3)))).mean() < 0.25
 
 
+def _host_sphere_filter(c, r2):
+    """host side of the filter (scene_tables.cpp build_scene_tables): g (the box holds the spheres, not
+    only their centres) and rho_max, c' = fl(c - g), km rounded up from double"""
+    cd, rd = c.astype(np.float64), np.sqrt(np.maximum(0.0, r2.astype(np.float64)))
+    g, rho = _scene_box((cd - rd[:, None]).min(axis=0), (cd + rd[:, None]).max(axis=0))
+    cp = (c.astype(np.float64) - g.astype(np.float64)).astype(f32)
+    c2 = (cp.astype(np.float64) ** 2).sum(axis=1)
+    km_d = r2.astype(np.float64) - c2 + 2.0 ** -16 * (c2 + np.abs(r2.astype(np.float64))) + 2.0 ** -120
+    km = km_d.astype(f32)
+    low = km.astype(np.float64) < km_d
+    km[low] = np.nextafter(km[low], f32(np.inf))
+    return g, rho, cp, km
+
+
+def _assert_library_sphere_filter(c, r):
+    """the restatement above == the library's DevSphPairF table and header, bit for bit"""
+    import esctp1raytracer_amd as esc
+    sc = esc.Scene()
+    sc.add_spheres(np.column_stack([c, r]), np.zeros((len(c), 13), f32))
+    g, rho, cp, km = _host_sphere_filter(c, f32(r * r))
+    lib_g, lib_rho = _library_header(sc)
+    assert _same_bits(lib_g, g) and lib_rho == f32(rho)
+    assert _same_bits(_pair_records(sc.table("sph2_f"), 4, len(c)), np.column_stack([cp, km]))
+
+
 @pytest.mark.parametrize("scale,offset", [(1.0, 0.0), (30.0, 0.0), (30.0, 500.0), (1000.0, 0.0)])
 def test_shadow_filter_never_rejects_a_reference_candidate(scale, offset):
-    """commit()'s DevSphPairF + make_ray_filter + pair4_any_filter_pk vs the reference's 16-op
+    """build_scene_tables' DevSphPairF + make_ray_filter + pair4_any_filter_pk vs the reference's 16-op
     shadow test (oc = o - c; b = dot(oc, L); cc = dot(oc, oc) - r2; disc = b*b - cc).  `offset`
     moves the whole scene away from the world origin: the filter works relative to the scene
     point g, so its margins must not care."""
@@ -114,14 +188,8 @@ def test_shadow_filter_never_rejects_a_reference_candidate(scale, offset):
     cc = f32(ref_dot(ocx, ocy, ocz, ocx, ocy, ocz) - r2)
     disc = f32(f32(b * b) - cc)
     ref_candidate = ~(disc < 0)
-    # host side of the filter (rt_capi.cpp commit()): g, c' = fl(c - g), km rounded up from double
-    g = (0.5 * (c.min(axis=0).astype(np.float64) + c.max(axis=0).astype(np.float64))).astype(f32)
-    cp = (c.astype(np.float64) - g.astype(np.float64)).astype(f32)
-    c2 = (cp.astype(np.float64) ** 2).sum(axis=1)
-    km_d = r2.astype(np.float64) - c2 + 2.0 ** -16 * (c2 + np.abs(r2.astype(np.float64))) + 2.0 ** -120
-    km = km_d.astype(f32)
-    low = km.astype(np.float64) < km_d
-    km[low] = np.nextafter(km[low], f32(np.inf))
+    g, _, cp, km = _host_sphere_filter(c, r2)
+    _assert_library_sphere_filter(c[:N_CROSS], r[:N_CROSS])
     # device side (make_ray_filter, un-fused) ...
     ax, ay, az = f32(o[:, 0] - g[0]), f32(o[:, 1] - g[1]), f32(o[:, 2] - g[2])
     nn = ref_dot(ax, ay, az, ax, ay, az)
@@ -211,7 +279,7 @@ def test_primary_group_filter_never_rejects_a_member_candidate(scale, spread):
 
 @pytest.mark.parametrize("scale,offset", [(1.0, 0.0), (30.0, 0.0), (30.0, 500.0), (1000.0, 0.0)])
 def test_shadow_group_filter_never_rejects_a_member_candidate(scale, offset):
-    """rt_device.h SphGroups, shadow rays of the last light: commit()'s bounding-sphere record in
+    """rt_device.h SphGroups, shadow rays of the last light: build_scene_tables' bounding-sphere record in
     DevSphPairF form (R = rgeo + 0x1.6p-10 (rho_max + |C - g| + rgeo) + 2^-60) against the reference's
     16-op test of every member, for origins inside the scene box (|fl(O - g)|_1 <= rho_max)."""
     rng = np.random.default_rng(11 + int(scale) + int(offset))
@@ -230,7 +298,7 @@ def test_shadow_group_filter_never_rejects_a_member_candidate(scale, offset):
         b = ref_dot(ocx, ocy, ocz, L[:, 0], L[:, 1], L[:, 2])
         cc = f32(ref_dot(ocx, ocy, ocz, ocx, ocy, ocz) - r2[:, m])
         any_cand |= ~(f32(f32(b * b) - cc) < 0)
-    # host side: g and rho_max as commit() takes them (box of everything, 1-norm radius doubled)
+    # host side: g and rho_max as build_scene_tables takes them (box of everything, 1-norm radius doubled)
     rd = np.sqrt(r2.astype(np.float64))
     lo = np.minimum((c.astype(np.float64) - rd[..., None]).min(axis=(0, 1)), o.min(axis=0))
     hi = np.maximum((c.astype(np.float64) + rd[..., None]).max(axis=(0, 1)), o.max(axis=0))
@@ -398,10 +466,36 @@ def test_triangle_primary_filter_never_rejects_a_reference_candidate(scale, size
     assert ok.mean() < 0.5
 
 
+def _host_triangle_filter(v0, e1, e2, g, rho):
+    """host side (scene_tables.cpp build_tri2f): the record in double -> fp32, M rounded up"""
+    vd = (v0.astype(np.float64) - g).astype(f32).astype(np.float64)
+    e1d, e2d = e1.astype(np.float64), e2.astype(np.float64)
+    n1 = np.cross(e2d, e1d).astype(f32)
+    k1 = np.cross(e1d, vd).astype(f32)
+    k2 = np.cross(e2d, vd).astype(f32)
+    a1, a2, av = np.abs(e1d).sum(1), np.abs(e2d).sum(1), np.abs(vd).sum(1)
+    p12 = a1 * a2
+    Md = 2.0 ** -17 * p12 * (p12 + (a1 + a2) * (av + rho)) + 2.0 ** -120
+    M = Md.astype(f32)
+    low = M.astype(np.float64) < Md
+    M[low] = np.nextafter(M[low], f32(np.inf))
+    return n1, k1, k2, M
+
+
+def _assert_library_triangle_filter(v0, e1, e2):
+    """g, rho_max and the restatement above == the library's header and DevTriPairF table, bit for bit"""
+    sc, e1, e2 = _triangle_scene(v0, e1, e2)
+    g, rho = _scene_box(*_triangle_box(v0, e1, e2))
+    lib_g, lib_rho = _library_header(sc)
+    assert _same_bits(lib_g, g) and lib_rho == f32(rho)
+    n1, k1, k2, M = _host_triangle_filter(v0, e1, e2, g, rho)
+    assert _same_bits(_pair_records(sc.table("tri2_f"), 16, len(v0)), np.column_stack([n1, e1, e2, k1, k2, M]))
+
+
 @pytest.mark.parametrize("scale,size,offset", [(1.0, 1.0, 0.0), (30.0, 0.1, 0.0), (30.0, 5.0, 800.0),
                                                (1000.0, 0.01, 0.0)])
 def test_triangle_shadow_filter_never_rejects_a_reference_candidate(scale, size, offset):
-    """commit()'s DevTriPairF + make_ray_tri_filter + tripair2_any_filter_pk vs ray_triangle.h's
+    """build_scene_tables' DevTriPairF + make_ray_tri_filter + tripair2_any_filter_pk vs ray_triangle.h's
     numerators for arbitrary origins (test_tri_any), rays inside rho_max."""
     rng = np.random.default_rng(int(scale + size * 10 + offset))
     n = 1_000_000
@@ -419,22 +513,9 @@ def test_triangle_shadow_filter_never_rejects_a_reference_candidate(scale, size,
     qv = ref_cross(*tv, e1[:, 0], e1[:, 1], e1[:, 2])
     vn = ref_dot(Lx, Ly, Lz, *qv)
     ref_ok = uv_accept(det, un, vn)
-    # host side (commit()): g, rho_max, record in double -> fp32, M rounded up
-    pts = np.concatenate([v0, v0 + e1, v0 + e2]).astype(np.float64)
-    lo, hi = pts.min(axis=0), pts.max(axis=0)
-    g = (0.5 * (lo + hi)).astype(f32)
-    rho = 2.0 * np.maximum(hi - g, g - lo).sum() + 1e-30
-    vd = (v0.astype(np.float64) - g).astype(f32).astype(np.float64)
-    e1d, e2d = e1.astype(np.float64), e2.astype(np.float64)
-    n1 = np.cross(e2d, e1d).astype(f32)
-    k1 = np.cross(e1d, vd).astype(f32)
-    k2 = np.cross(e2d, vd).astype(f32)
-    a1, a2, av = np.abs(e1d).sum(1), np.abs(e2d).sum(1), np.abs(vd).sum(1)
-    p12 = a1 * a2
-    Md = 2.0 ** -17 * p12 * (p12 + (a1 + a2) * (av + rho)) + 2.0 ** -120
-    M = Md.astype(f32)
-    low = M.astype(np.float64) < Md
-    M[low] = np.nextafter(M[low], f32(np.inf))
+    g, rho = _scene_box(*_triangle_box(v0, e1, e2))
+    n1, k1, k2, M = _host_triangle_filter(v0, e1, e2, g, rho)
+    _assert_library_triangle_filter(v0[:N_CROSS], e1[:N_CROSS], e2[:N_CROSS])
     # device side: a = o - g, m = a x L (un-fused), then the FMA chains
     a = [f32(o[:, i] - g[i]) for i in range(3)]
     assert float((np.abs(a[0]) + np.abs(a[1]) + np.abs(a[2])).max()) <= rho  # not `far`
@@ -543,9 +624,48 @@ def test_triangle_primary_prefilter_never_rejects_a_reference_candidate(scale, s
         assert ((np.abs(br) >= 1) | (np.abs(gr) <= 1))[~thin].mean() < 0.2
 
 
+def _host_triangle_prefilter(v0, e1, e2, g, rho):
+    """host side (scene_tables.cpp build_tri2pf), double: the bounding sphere's centre G - g and km, the
+    normal over tau'; a sliver (the shape test fails) is always a candidate"""
+    e1d, e2d = e1.astype(np.float64), e2.astype(np.float64)
+    s3, rad, emax = _tri_geometry(e1, e2)
+    G = v0.astype(np.float64) + s3
+    a1, a2 = np.abs(e1d).sum(1), np.abs(e2d).sum(1)
+    av = np.abs((v0.astype(np.float64) - g).astype(f32).astype(np.float64)).sum(1)
+    u = 2.0 ** -24
+    at, p12 = rho + av, a1 * a2
+    ok_shape = rad > 2.0 ** -10 * emax
+    with np.errstate(all="ignore"):
+        tau = 3.2 * u * (10.04 * at * a2 + 5.04 * at * a1 + 20.1 * p12) * emax / rad
+    taup = (tau + 10.1 * u * p12) * 1.00001 + 2.0 ** -120
+    R = 2.0 * rad + 8.0 * u * (at + a1 + a2)
+    c = (G - g).astype(f32)
+    c2 = (c.astype(np.float64) ** 2).sum(1)
+    R2 = R * R * 1.00001
+    km_d = R2 - c2 + 2.0 ** -16 * (c2 + R2) + 2.0 ** -120
+    km = km_d.astype(f32)
+    low = km.astype(np.float64) < km_d
+    km[low] = np.nextafter(km[low], f32(np.inf))
+    km = np.where(ok_shape, km, f32(np.inf))
+    n1 = np.cross(e2d, e1d)
+    with np.errstate(all="ignore"):
+        gv = np.where(ok_shape[:, None], (n1 / taup[:, None]), 0.0).astype(f32)
+    cc = np.where(ok_shape[:, None], c, f32(0))
+    return cc, km, gv
+
+
+def _assert_library_triangle_prefilter(v0, e1, e2):
+    """the restatement above == the library's DevTriPairPF table, bit for bit"""
+    sc, e1, e2 = _triangle_scene(v0, e1, e2)
+    g, rho = _scene_box(*_triangle_box(v0, e1, e2))
+    cc, km, gv = _host_triangle_prefilter(v0, e1, e2, g, rho)
+    rec = _pair_records(sc.table("tri2_pf"), 8, len(v0))
+    assert _same_bits(rec[:, :7], np.column_stack([cc, km, gv])) and not rec[:, 7].any()
+
+
 @pytest.mark.parametrize("scale,size,offset", [(1.0, 1.0, 0.0), (30.0, 0.1, 0.0), (30.0, 5.0, 800.0)])
 def test_triangle_shadow_prefilter_never_rejects_a_reference_candidate(scale, size, offset):
-    """commit()'s DevTriPairPF + make_ray_filter + tripair2_any_prefilter_pk: bounding sphere in
+    """build_scene_tables' DevTriPairPF + make_ray_filter + tripair2_any_prefilter_pk: bounding sphere in
     the shadow-sphere filter's form OR nearly parallel, for arbitrary origins inside rho_max."""
     rng = np.random.default_rng(int(scale * 3 + size * 17 + offset))
     n = 1_000_000
@@ -571,35 +691,9 @@ def test_triangle_shadow_prefilter_never_rejects_a_reference_candidate(scale, si
     qv = ref_cross(*tv, e1[:, 0], e1[:, 1], e1[:, 2])
     vn = ref_dot(Lx, Ly, Lz, *qv)
     ref_ok = uv_accept(det, un, vn)
-    # host side (commit()), double
-    pts = np.concatenate([v0, v0 + e1, v0 + e2]).astype(np.float64)
-    lo, hi = pts.min(axis=0), pts.max(axis=0)
-    g = (0.5 * (lo + hi)).astype(f32)
-    rho = 2.0 * np.maximum(hi - g, g - lo).sum() + 1e-30
-    e1d, e2d = e1.astype(np.float64), e2.astype(np.float64)
-    s3, rad, emax = _tri_geometry(e1, e2)
-    G = v0.astype(np.float64) + s3
-    a1, a2 = np.abs(e1d).sum(1), np.abs(e2d).sum(1)
-    av = np.abs((v0.astype(np.float64) - g).astype(f32).astype(np.float64)).sum(1)
-    u = 2.0 ** -24
-    at, p12 = rho + av, a1 * a2
-    ok_shape = rad > 2.0 ** -10 * emax
-    with np.errstate(all="ignore"):
-        tau = 3.2 * u * (10.04 * at * a2 + 5.04 * at * a1 + 20.1 * p12) * emax / rad
-    taup = (tau + 10.1 * u * p12) * 1.00001 + 2.0 ** -120
-    R = 2.0 * rad + 8.0 * u * (at + a1 + a2)
-    c = (G - g).astype(f32)
-    c2 = (c.astype(np.float64) ** 2).sum(1)
-    R2 = R * R * 1.00001
-    km_d = R2 - c2 + 2.0 ** -16 * (c2 + R2) + 2.0 ** -120
-    km = km_d.astype(f32)
-    low = km.astype(np.float64) < km_d
-    km[low] = np.nextafter(km[low], f32(np.inf))
-    km = np.where(ok_shape, km, f32(np.inf))
-    n1 = np.cross(e2d, e1d)
-    with np.errstate(all="ignore"):
-        gv = np.where(ok_shape[:, None], (n1 / taup[:, None]), 0.0).astype(f32)
-    cc = np.where(ok_shape[:, None], c, f32(0))
+    g, rho = _scene_box(*_triangle_box(v0, e1, e2))
+    cc, km, gv = _host_triangle_prefilter(v0, e1, e2, g, rho)
+    _assert_library_triangle_prefilter(v0[:N_CROSS], e1[:N_CROSS], e2[:N_CROSS])
     # device side: make_ray_filter + tripair2_any_prefilter_pk
     ax, ay, az = f32(o[:, 0] - g[0]), f32(o[:, 1] - g[1]), f32(o[:, 2] - g[2])
     assert float((np.abs(ax) + np.abs(ay) + np.abs(az)).max()) <= rho
@@ -804,7 +898,7 @@ def test_triangle_primary_group_never_rejects_a_member_candidate(scale, size, wi
                                                     (30.0, 3.0, 0.0, True), (30.0, 3.0, 400.0, True),
                                                     (30.0, 3.0, 0.0, False)])
 def test_triangle_shadow_group_never_rejects_a_member_candidate(scale, size, offset, cone):
-    """rt_device.h TriGroups, shadow rays: commit()'s group record in DevTriPairPF form (bounding
+    """rt_device.h TriGroups, shadow rays: build_scene_tables' group record in DevTriPairPF form (bounding
     sphere with R = rgeo + 8u at in the q' form, cone axis over kappa' = (smax + b0 + b1 at +
     2^-20) 1.0001, at = rho_max + |C - g|_1 + rext) against the reference's any-hit accept of a
     member, for origins inside the scene box -- on member planes and off them -- and rays that
@@ -848,7 +942,7 @@ def test_triangle_shadow_group_never_rejects_a_member_candidate(scale, size, off
     tv = [f32(o[:, i] - v0[:, i]) for i in range(3)]
     qv = ref_cross(*tv, e1[:, 0], e1[:, 1], e1[:, 2])
     ref_ok = uv_accept(det, ref_dot(*tv, *pv), ref_dot(Lx, Ly, Lz, *qv))
-    # host side (commit()): g, rho_max over everything; the group record in double
+    # host side (build_scene_tables): g, rho_max over everything; the group record in double
     pts = np.concatenate([V0.reshape(-1, 3), (V0 + E1).reshape(-1, 3), (V0 + E2).reshape(-1, 3),
                           o]).astype(np.float64)
     lo, hi = pts.min(axis=0), pts.max(axis=0)
