@@ -173,8 +173,16 @@ def test_light_lists_awkward_lights(esc, renderer, case):
                             [(0, 9, -20), (0.5, 9, -20), (0, 9, -20.5)]],
             "light far outside": [far], "light level with the floor": [low]}[case]
     d = _spheres_with_lights(esc, tris)
-    if case == "light inside a sphere":
+    if case == "light inside a sphere's reach":
+        before = d["spheres"][0].copy()
         d["spheres"][0] = (0.1, 2.6, -9.8, 0.29)  # the sample point (-0.2, 2.6, -9.8) is 0.01 outside it
+        assert not np.array_equal(before, d["spheres"][0]), "sphere 0 was not moved"
+        P = ol.scene_to_product(d).table("light_points").view(np.float32).reshape(-1, 4)[0, :3].astype(float)
+        c, r = d["spheres"][0, :3].astype(float), float(d["spheres"][0, 3])
+        pts = np.concatenate([g["vertex"] for g in d["geometry"]] + [d["spheres"][:, :3]]).astype(float)
+        far = np.linalg.norm(np.maximum(np.abs(pts.max(0) - c), np.abs(pts.min(0) - c)))
+        gap = np.linalg.norm(P - c) - r  # rt_lists.h: reach = r (1 + u) + 0x1.6p-10 W_i + delta, W_i >= far
+        assert 0.0 < gap < float.fromhex("0x1.6p-10") * far, (gap, far)
     eye, look = esc.synthetic_view()
     ref, st = both_ways(esc, renderer, d, eye, look, 224, 128, f"light lists/{case}")
     assert st[2] is not None, "no light lists were built"
