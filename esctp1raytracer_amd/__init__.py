@@ -18,7 +18,7 @@ from ._capi import (ESC_FACE_FIXED, ESC_FACE_HASH, ESC_STAGE_AUTO, ESC_STAGE_BVH
                     ESC_STAGE_SMEM, ESC_TRANSMIT_OFF, ESC_TRANSMIT_REFRACT, ESC_TRANSMIT_FRESNEL, EscError,
                     check)
 
-__all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "trace", "write_ppm", "quantise", "synthetic_view",
+__all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table",
            "EscError", "ESC_FACE_FIXED", "ESC_FACE_HASH", "ESC_STAGE_AUTO", "ESC_STAGE_SMEM",
            "ESC_STAGE_LDS", "ESC_STAGE_BVH", "ESC_RENDER_EXACT_ONLY", "ESC_RENDER_TIME_KERNELS", "ESC_RENDER_INDEX_ORDER", "ESC_RENDER_SHADE_QUEUE",
            "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "ESC_TRANSMIT_OFF", "ESC_TRANSMIT_REFRACT", "ESC_TRANSMIT_FRESNEL", "version"]
@@ -259,6 +259,18 @@ def synthetic_view():
     look = np.zeros(3, np.float32)
     _capi.load().esc_synthetic_view(_fp(eye), _fp(look))
     return eye, look
+
+
+def ambient_table(sets, samples, seed=0):
+    """esc_ambient_cosine_table: (sets, samples, 3) float32 cosine-weighted unit vectors about +z, made on the
+    host (no GPU needed) and deterministic in (sets, samples, seed).  Renderer.set_ambient_table takes it,
+    or any other array of local directions of that shape."""
+    out = np.zeros((int(sets), int(samples), 3), np.float32) if sets > 0 and samples > 0 else np.zeros(3, np.float32)
+    check(_capi.load().esc_ambient_cosine_table(int(sets), int(samples), int(seed) & (2 ** 64 - 1), _fp(out)))
+    return out
+
+
+FLT_MAX = float(np.finfo(np.float32).max)
 
 
 def _options(shadows, face_mode, fixed_face, seed, stage, px=0, flags=0):
@@ -641,6 +653,106 @@ class Renderer:
         check(self._lib.esc_last_adaptive_stats(self._h, C.byref(s)))
         return {k: int(getattr(s, k)) for k in ("pixels", "refined_pixels", "samples", "hit_rays", "shadow_rays",
                                                 "exact_rays", "exact_tests")}
+
+    # ---- ambient occlusion (esc_ambient_rays / esc_render_ambient / esc_modulate) -----------------------
+    def set_ambient_table(self, table):
+        """esc_set_ambient_table: table is a (sets, samples, 3) float32 array of local directions about +z
+        (ambient_table makes a cosine-weighted one), 1 <= sets, samples <= 64.  It belongs to the renderer
+        and survives uploads of other scenes.  Its contents are not validated."""
+        t = np.ascontiguousarray(table, dtype=np.float32)
+        if t.ndim != 3 or t.shape[2] != 3:
+            raise ValueError("table must have shape (sets, samples, 3)")
+        check(self._lib.esc_set_ambient_table(self._h, t.shape[0], t.shape[1], _fp(t)))
+        self._ambient_shape = (t.shape[0], t.shape[1])
+
+    def _ambient_options(self, samples, sets, radius, bias, seed, pixel_base, exact):
+        s0, k0 = getattr(self, "_ambient_shape", (0, 0))
+        return _capi.esc_ambient_options(int(k0 if samples is None else samples), int(s0 if sets is None else sets),
+                                         float(radius), float(bias), int(seed) & (2 ** 64 - 1),
+                                         int(pixel_base) & 0xffffffff, ESC_RENDER_EXACT_ONLY if exact else 0)
+
+    def ambient_rays(self, origins, dirs, vis, *, radius=FLT_MAX, bias=1e-4, count=None, t=None, geom=None,
+                     prim=None, samples=None, sets=None, seed=0, pixel_base=0, exact=False):
+        """Ambient occlusion of n rays (esc_ambient_rays), asynchronous on the renderer's stream: of the K
+        directions of the table's set drawn for each ray, rotated about the hit's normal, how many reach
+        `radius` (FLT_MAX: unbounded) from the hit point, moved `bias` off its surface, without meeting a
+        primitive.  Contiguous device tensors: origins, dirs (n, 3) float32; outputs vis (n,) float32 =
+        count / K (1 for a miss), count (n,) int32 or None, t (n,) float32, geom, prim (n,) int32 or None
+        (intersect_rays' values).  samples, sets: K and S, None = the table's.  exact=True: every ray
+        through the reference loop."""
+        import torch
+        n, po, pd, _ = self._query_inputs(origins, dirs, None)
+        args = (self._query_ptr("vis", vis, torch.float32, (n,)),
+                None if count is None else self._query_ptr("count", count, torch.int32, (n,)),
+                None if t is None else self._query_ptr("t", t, torch.float32, (n,)),
+                None if geom is None else self._query_ptr("geom", geom, torch.int32, (n,)),
+                None if prim is None else self._query_ptr("prim", prim, torch.int32, (n,)))
+        o = self._ambient_options(samples, sets, radius, bias, seed, pixel_base, exact)
+        check(self._lib.esc_ambient_rays(self._h, n, po, pd, C.byref(o), *args))
+
+    def ambient(self, origins, dirs, *, radius=FLT_MAX, bias=1e-4, samples=None, sets=None, seed=0, pixel_base=0,
+                exact=False):
+        """Synchronous ambient occlusion of numpy rays: {"vis", "count", "t", "geom", "prim"} as numpy arrays."""
+        import torch
+        to, td, _ = self._stage(origins, dirs, None)
+        n = to.shape[0]
+        dev = to.device
+        vis = torch.empty(n, dtype=torch.float32, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        t = torch.empty(n, dtype=torch.float32, device=dev)
+        geom = torch.empty(n, dtype=torch.int32, device=dev)
+        prim = torch.empty(n, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the buffers were made on torch's stream
+        self.ambient_rays(to, td, vis, radius=radius, bias=bias, count=count, t=t, geom=geom, prim=prim,
+                          samples=samples, sets=sets, seed=seed, pixel_base=pixel_base, exact=exact)
+        self.synchronize()
+        return {"vis": vis.cpu().numpy(), "count": count.cpu().numpy(), "t": t.cpu().numpy(),
+                "geom": geom.cpu().numpy(), "prim": prim.cpu().numpy()}
+
+    def render_ambient(self, camera, W, H, *, radius=FLT_MAX, bias=1e-4, samples=None, sets=None, seed=0,
+                       want_count=False, exact=False):
+        """Pixel-centre visibility of a frame (esc_render_ambient): ambient_rays on camera_rays(camera, W, H)
+        with pixel ids h * W + w, the rays made inside the kernel.  Returns numpy float32 (H, W), and the
+        int32 (H, W) counts when asked for.  Synchronous."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        vis = torch.empty((H, W), dtype=torch.float32, device=dev)
+        count = torch.empty((H, W), dtype=torch.int32, device=dev) if want_count else None
+        o = self._ambient_options(samples, sets, radius, bias, seed, 0, exact)
+        torch.cuda.current_stream(dev).synchronize()  # the buffers were made on torch's stream
+        check(self._lib.esc_render_ambient(self._h, C.byref(camera.c), W, H, C.byref(o), C.c_void_p(vis.data_ptr()),
+                                           None if count is None else C.c_void_p(count.data_ptr())))
+        self.synchronize()
+        return (vis.cpu().numpy(), count.cpu().numpy()) if want_count else vis.cpu().numpy()
+
+    def modulate(self, image, vis, *, want_u8=False):
+        """image * vis per pixel and channel on the GPU (esc_modulate): image (..., 3) float32 and vis (...)
+        float32 numpy arrays of the same pixels.  Returns the float32 product, and its quantised bytes when
+        asked for.  Synchronous."""
+        import torch
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        v = np.ascontiguousarray(vis, dtype=np.float32)
+        if img.shape[-1:] != (3,) or img.shape[:-1] != v.shape:
+            raise ValueError("image must have shape vis.shape + (3,)")
+        dev = torch.device("cuda", self.device)
+        ti = torch.from_numpy(img).to(dev)
+        tv = torch.from_numpy(v).to(dev)
+        out = torch.empty_like(ti)
+        u8 = torch.empty(img.shape, dtype=torch.uint8, device=dev) if want_u8 else None
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.esc_modulate(self._h, v.size, C.c_void_p(ti.data_ptr()), C.c_void_p(tv.data_ptr()),
+                                     C.c_void_p(out.data_ptr()), None if u8 is None else C.c_void_p(u8.data_ptr())))
+        self.synchronize()
+        return (out.cpu().numpy(), u8.cpu().numpy()) if want_u8 else out.cpu().numpy()
+
+    def ambient_stats(self):
+        """Counts of the last ambient_rays / render_ambient call: rays, hit_rays, samples (K * hit_rays),
+        occluded_samples, exact_rays (primary or sample rays that took the reference loop), exact_tests.
+        Synchronises."""
+        s = _capi.esc_ambient_stats()
+        check(self._lib.esc_last_ambient_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k in ("rays", "hit_rays", "samples", "occluded_samples", "exact_rays",
+                                                "exact_tests")}
 
     def trace_rays(self, origins, dirs, rgb, *, max_depth, bias, rgb8=None, pixel_base=0, shadows=True,
                    face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False, transmission="off"):

@@ -128,6 +128,16 @@ class esc_adaptive_stats(C.Structure):  # 56 bytes
                 ("exact_tests", C.c_uint64)]
 
 
+class esc_ambient_options(C.Structure):  # 32 bytes
+    _fields_ = [("samples", C.c_int32), ("sets", C.c_int32), ("radius", C.c_float), ("bias", C.c_float),
+                ("seed", C.c_uint64), ("pixel_base", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class esc_ambient_stats(C.Structure):  # 48 bytes
+    _fields_ = [("rays", C.c_uint64), ("hit_rays", C.c_uint64), ("samples", C.c_uint64),
+                ("occluded_samples", C.c_uint64), ("exact_rays", C.c_uint64), ("exact_tests", C.c_uint64)]
+
+
 class esc_bvh_node(C.Structure):  # 64 bytes
     _fields_ = [("lo0", C.c_float * 3), ("hi0", C.c_float * 3), ("lo1", C.c_float * 3),
                 ("hi1", C.c_float * 3), ("child", C.c_int32 * 2), ("minkey", C.c_uint32 * 2)]
@@ -240,6 +250,13 @@ SIGNATURES = {
     "esc_render_traced_ex": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(esc_render_options), C.POINTER(esc_trace_options), _P, _P]),
     "esc_last_transmit_stats": (C.c_int, [_P, C.POINTER(esc_transmit_stats)]),
+    "esc_set_ambient_table": (C.c_int, [_P, C.c_int32, C.c_int32, _F]),
+    "esc_ambient_cosine_table": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, _F]),
+    "esc_ambient_rays": (C.c_int, [_P, C.c_int64, _P, _P, C.POINTER(esc_ambient_options), _P, _P, _P, _P, _P]),
+    "esc_render_ambient": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
+                                     C.POINTER(esc_ambient_options), _P, _P]),
+    "esc_modulate": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    "esc_last_ambient_stats": (C.c_int, [_P, C.POINTER(esc_ambient_stats)]),
     "esc_render_frame_host": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
                                         C.POINTER(esc_render_options), _F, _U8]),
     "esc_render_frame_multi": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,

@@ -17,6 +17,7 @@
 #include "../host/scene.h"
 #include "../host/scene_tables.h"
 #include "rt_adaptive.h"
+#include "rt_ambient.h"
 #include "rt_device.h"
 #include "rt_query.h"
 #include "rt_shade_rays.h"
@@ -56,6 +57,8 @@ extern "C" int esc_launch_trace_level(const esc::TraceParams *p, hipStream_t str
 extern "C" int esc_launch_adaptive_mask(const esc::AdaptiveMaskParams *p, hipStream_t stream);
 extern "C" int esc_launch_adaptive_list(const esc::AdaptiveListParams *p, hipStream_t stream);
 extern "C" int esc_launch_adaptive_refine(const esc::AdaptiveRefineParams *p, hipStream_t stream);
+extern "C" int esc_launch_ambient(const esc::AmbientParams *p, int camera, hipStream_t stream);
+extern "C" int esc_launch_modulate(const esc::ModulateParams *p, hipStream_t stream);
 extern "C" int esc_launch_assemble(const void *gathered, void *frame, size_t rank_pitch_bytes,
                                    int n_ranks, int H, int strip_rows, size_t row_bytes,
                                    hipStream_t stream);
@@ -190,6 +193,13 @@ struct esc_context {
   size_t ad_bytes = 0;
   uint64_t ad_pixels = 0;
   int32_t ad_spp = 0;
+  // ambient occlusion (rt_ambient.hip): the sample table of esc_set_ambient_table (am_sets x am_samples x 3
+  // floats; the context's, not the scene's: an upload leaves it alone), esc_ambient_stats' device
+  // counters and the last call's K
+  float *d_am_table = nullptr;
+  int32_t am_sets = 0, am_samples = 0;
+  unsigned long long *d_amstats = nullptr;
+  int32_t am_k = 0;
 };
 
 namespace {
@@ -492,7 +502,7 @@ void esc_context_destroy(esc_context *ctx) {
                   ctx->d_tri_boxes, ctx->d_sph_boxes, ctx->d_bin_hdr, ctx->d_bin_tri_ids,
                   ctx->d_bin_sph_ids, ctx->lbins.face_hdr, ctx->lbins.counts, ctx->lbins.tri_ids,
                   ctx->lbins.sph_ids, ctx->d_qstats, ctx->d_sstats, ctx->d_ss, ctx->d_tstats, ctx->d_tr,
-                  ctx->d_transmit, ctx->d_astats, ctx->d_ad};
+                  ctx->d_transmit, ctx->d_astats, ctx->d_ad, ctx->d_am_table, ctx->d_amstats};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t ev : ctx->ev)
@@ -2301,6 +2311,274 @@ int esc_render_traced_ex(esc_context *ctx, const esc_camera *cam, int32_t W, int
   if (rc) return rc;
   return render_traced_impl(fn, ctx, cam, W, H, spp, topts->max_depth, topts->bias, topts->transmission, opts,
                             d_image, d_u8);
+}
+
+// ---- ambient occlusion (rt_ambient.hip) ------------------------------------------------------------
+int esc_ambient_cosine_table(int32_t sets, int32_t samples, uint64_t seed, float *out) {
+  const char *fn = "esc_ambient_cosine_table";
+  if (sets < 1 || sets > esc::kAmbientMaxDim || samples < 1 || samples > esc::kAmbientMaxDim) {
+    set_error(std::string(fn) + ": sets and samples must be in 1..64");
+    return ESC_ERR_INVALID;
+  }
+  if (!out) {
+    set_error(std::string(fn) + ": out is null");
+    return ESC_ERR_INVALID;
+  }
+  // splitmix64 from (seed, sets, samples); u = (x >> 11 + 1/2) * 2^-53 in (0, 1).  Malley's method: a
+  // uniform point of the unit disc lifted to the hemisphere is cosine-weighted.
+  uint64_t st = seed ^ ((uint64_t)sets << 48) ^ ((uint64_t)samples << 40);
+  auto next = [&st]() {
+    uint64_t z = (st += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return ((double)(z >> 11) + 0.5) * 0x1p-53;
+  };
+  const double two_pi = 6.283185307179586476925286766559;
+  for (int64_t j = 0; j < (int64_t)sets * samples; ++j) {
+    const double u1 = next(), u2 = next();
+    const double r = std::sqrt(u1), phi = two_pi * u2;
+    double v[3] = {r * std::cos(phi), r * std::sin(phi), std::sqrt(1.0 - u1)};
+    const double len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    for (int c = 0; c < 3; ++c) out[3 * j + c] = (float)(v[c] / len);
+  }
+  return ESC_OK;
+}
+
+int esc_set_ambient_table(esc_context *ctx, int32_t sets, int32_t samples, const float *host_table) {
+  const char *fn = "esc_set_ambient_table";
+  if (!ctx) {
+    set_error(std::string(fn) + ": ctx is null");
+    return ESC_ERR_INVALID;
+  }
+  if (sets < 1 || sets > esc::kAmbientMaxDim || samples < 1 || samples > esc::kAmbientMaxDim) {
+    set_error(std::string(fn) + ": sets and samples must be in 1..64");
+    return ESC_ERR_INVALID;
+  }
+  if (!host_table) {
+    set_error(std::string(fn) + ": host_table is null");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream)); // a call in flight may still read the old table
+  const size_t bytes = (size_t)sets * samples * 3 * sizeof(float);
+  if (ctx->d_am_table) HIP_TRY(hipFree(ctx->d_am_table));
+  ctx->d_am_table = nullptr;
+  ctx->am_sets = ctx->am_samples = 0;
+  HIP_TRY(hipMalloc((void **)&ctx->d_am_table, bytes));
+  HIP_TRY(hipMemcpyAsync(ctx->d_am_table, host_table, bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream)); // host_table is the caller's again
+  ctx->am_sets = sets;
+  ctx->am_samples = samples;
+  return ESC_OK;
+}
+
+// the checks esc_ambient_rays and esc_render_ambient share, after ctx and opts are known not to be null
+static int ambient_options_ok(const esc_context *ctx, const char *fn_, const esc_ambient_options *o) {
+  const std::string fn(fn_);
+  if (!ctx->have_scene) {
+    set_error(fn + ": no scene uploaded (esc_upload_scene / esc_upload_flat)");
+    return ESC_ERR_INVALID;
+  }
+  if (!ctx->d_am_table) {
+    set_error(fn + ": no sample table (esc_set_ambient_table)");
+    return ESC_ERR_INVALID;
+  }
+  if (o->samples < 1 || o->samples > ctx->am_samples) {
+    set_error(fn + ": samples must be in 1 .. the table's samples per set");
+    return ESC_ERR_INVALID;
+  }
+  if (o->sets < 1 || o->sets > ctx->am_sets) {
+    set_error(fn + ": sets must be in 1 .. the table's sets");
+    return ESC_ERR_INVALID;
+  }
+  if (!(o->radius > 0.f) || !std::isfinite(o->radius)) {
+    set_error(fn + ": radius must be a finite number > 0 (FLT_MAX: unbounded)");
+    return ESC_ERR_INVALID;
+  }
+  if (!(o->bias >= 0.f) || !std::isfinite(o->bias)) {
+    set_error(fn + ": bias must be a finite number >= 0");
+    return ESC_ERR_INVALID;
+  }
+  if (o->flags & ~(uint32_t)ESC_RENDER_EXACT_ONLY) {
+    set_error(fn + ": flags takes 0 or ESC_RENDER_EXACT_ONLY only");
+    return ESC_ERR_INVALID;
+  }
+  return ESC_OK;
+}
+
+// k_ambient on n rays of an already validated call: the caller's arrays, or (cam != nullptr) the frame's
+static int ambient_launch(esc_context *ctx, const char *fn, int64_t n, const float *d_origins, const float *d_dirs,
+                          const esc_camera *cam, int32_t W, int32_t H, const esc_ambient_options *o,
+                          uint32_t pixel_base, float *d_vis, int32_t *d_count, float *d_t, int32_t *d_geom,
+                          int32_t *d_prim) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!ctx->d_amstats)
+    HIP_TRY(hipMalloc((void **)&ctx->d_amstats, esc::kAmbientStats * sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(ctx->d_amstats, 0, esc::kAmbientStats * sizeof(unsigned long long), ctx->stream));
+  ctx->am_k = o->samples;
+  if (n == 0) return ESC_OK;
+  esc::AmbientParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.q.n = n;
+  p.q.orig = d_origins;
+  p.q.dir = d_dirs;
+  query_tables(ctx, p.q);
+  p.q.exact_only = (o->flags & ESC_RENDER_EXACT_ONLY) ? 1 : 0;
+  p.vis = d_vis;
+  p.count = d_count;
+  p.t = d_t;
+  p.geom = d_geom;
+  p.prim = d_prim;
+  p.tri_n = ctx->d_tri_n;
+  p.mat = ctx->d_mat;
+  p.table = ctx->d_am_table;
+  p.samples = o->samples;
+  p.sets = o->sets;
+  p.row_samples = ctx->am_samples;
+  p.radius = o->radius;
+  p.bias = o->bias;
+  p.seed = o->seed;
+  p.pixel_base = pixel_base;
+  if (cam) {
+    p.W = W;
+    p.H = H;
+    std::memcpy(p.origin, cam->origin, 12);
+    std::memcpy(p.llc, cam->lower_left_corner, 12);
+    std::memcpy(p.horizontal, cam->horizontal, 12);
+    std::memcpy(p.vertical, cam->vertical, 12);
+  }
+  // ESC_AMBIENT_STATS=0: nothing is counted (the A/B of tools/ambient_time.py; the stats then read zero)
+  const char *e = std::getenv("ESC_AMBIENT_STATS");
+  p.stats = (e && e[0] == '0') ? nullptr : ctx->d_amstats;
+  const int rc = esc_launch_ambient(&p, cam ? 1 : 0, ctx->stream);
+  if (rc) {
+    set_error(std::string(fn) + ": k_ambient launch: " + hipGetErrorString((hipError_t)rc));
+    return ESC_ERR_HIP;
+  }
+  return ESC_OK;
+}
+
+int esc_ambient_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs,
+                     const esc_ambient_options *opts, float *d_vis, int32_t *d_count, float *d_t,
+                     int32_t *d_geom, int32_t *d_prim) {
+  const char *fn = "esc_ambient_rays";
+  if (!ctx || !opts) {
+    set_error(!ctx ? "esc_ambient_rays: ctx is null" : "esc_ambient_rays: opts is null");
+    return ESC_ERR_INVALID;
+  }
+  if (n < 0) {
+    set_error("esc_ambient_rays: n < 0");
+    return ESC_ERR_INVALID;
+  }
+  const int rc = ambient_options_ok(ctx, fn, opts);
+  if (rc) return rc;
+  if (n > 0 && (!d_origins || !d_dirs || !d_vis)) {
+    set_error("esc_ambient_rays: d_origins, d_dirs and d_vis are required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_origins | (uintptr_t)d_dirs | (uintptr_t)d_vis | (uintptr_t)d_count | (uintptr_t)d_t |
+       (uintptr_t)d_geom | (uintptr_t)d_prim) & 3u) {
+    set_error("esc_ambient_rays: device pointers must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error("esc_ambient_rays: n exceeds one launch (2^32 - 1 workgroups of 256 rays)");
+    return ESC_ERR_INVALID;
+  }
+  return ambient_launch(ctx, fn, n, d_origins, d_dirs, nullptr, 0, 0, opts, opts->pixel_base, d_vis, d_count, d_t,
+                        d_geom, d_prim);
+}
+
+int esc_render_ambient(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
+                       const esc_ambient_options *opts, float *d_vis, int32_t *d_count) {
+  const char *fn_ = "esc_render_ambient";
+  const std::string fn(fn_);
+  if (!ctx || !cam || !opts || !d_vis) {
+    set_error(!ctx ? fn + ": ctx is null" : !opts ? fn + ": opts is null" : fn + ": cam or d_vis is null");
+    return ESC_ERR_INVALID;
+  }
+  if (W < 2 || H < 2) {
+    set_error(fn + ": need W,H >= 2");
+    return ESC_ERR_INVALID;
+  }
+  if ((int64_t)W * H > 0x7fffffffLL) {
+    set_error(fn + ": W*H exceeds the reference's int pixel index (main.cpp:784)");
+    return ESC_ERR_INVALID;
+  }
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(cam->origin[k]) || !std::isfinite(cam->lower_left_corner[k]) ||
+        !std::isfinite(cam->horizontal[k]) || !std::isfinite(cam->vertical[k])) {
+      set_error(fn + ": camera is not finite");
+      return ESC_ERR_INVALID;
+    }
+  const int rc = ambient_options_ok(ctx, fn_, opts);
+  if (rc) return rc;
+  if (((uintptr_t)d_vis | (uintptr_t)d_count) & 3u) {
+    set_error(fn + ": device pointers must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  return ambient_launch(ctx, fn_, (int64_t)W * H, nullptr, nullptr, cam, W, H, opts, 0u, d_vis, d_count, nullptr,
+                        nullptr, nullptr);
+}
+
+int esc_modulate(esc_context *ctx, int64_t n, const float *d_rgb, const float *d_vis, float *d_out,
+                 uint8_t *d_out8) {
+  if (!ctx) {
+    set_error("esc_modulate: ctx is null");
+    return ESC_ERR_INVALID;
+  }
+  if (n < 0) {
+    set_error("esc_modulate: n < 0");
+    return ESC_ERR_INVALID;
+  }
+  if (n > 0 && (!d_rgb || !d_vis || (!d_out && !d_out8))) {
+    set_error("esc_modulate: d_rgb, d_vis and one of d_out, d_out8 are required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_rgb | (uintptr_t)d_vis | (uintptr_t)d_out) & 3u) {
+    set_error("esc_modulate: device pointers must be 4-byte aligned (d_out8 excepted)");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error("esc_modulate: n exceeds one launch (2^32 - 1 workgroups of 256 pixels)");
+    return ESC_ERR_INVALID;
+  }
+  if (n == 0) return ESC_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  esc::ModulateParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.n = n;
+  p.rgb = d_rgb;
+  p.vis = d_vis;
+  p.out = d_out;
+  p.out8 = d_out8;
+  const int rc = esc_launch_modulate(&p, ctx->stream);
+  if (rc) {
+    set_error(std::string("esc_modulate: k_modulate launch: ") + hipGetErrorString((hipError_t)rc));
+    return ESC_ERR_HIP;
+  }
+  return ESC_OK;
+}
+
+int esc_last_ambient_stats(esc_context *ctx, esc_ambient_stats *out) {
+  if (!ctx || !out) {
+    set_error(!ctx ? "esc_last_ambient_stats: ctx is null" : "esc_last_ambient_stats: out is null");
+    return ESC_ERR_INVALID;
+  }
+  unsigned long long h[esc::kAmbientStats] = {0, 0, 0, 0, 0};
+  if (ctx->d_amstats) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_amstats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  out->rays = h[0];
+  out->hit_rays = h[1];
+  out->samples = h[1] * (uint64_t)ctx->am_k;
+  out->occluded_samples = h[2];
+  out->exact_rays = h[3];
+  out->exact_tests = h[4];
+  return ESC_OK;
 }
 
 int esc_reset_counters(esc_context *ctx) {

@@ -41,6 +41,13 @@
 //                 refract; total internal reflection reflects (esc_render_traced_ex, ESC_TRANSMIT_REFRACT)
 //   --fresnel     with --bounces: the same, and Schlick's term picks reflection or refraction per
 //                 sample by a hash (ESC_TRANSMIT_FRESNEL; use it with --spp).  Not with --refract
+//   --ao K        ambient occlusion: the image the run would otherwise write is multiplied, pixel by pixel,
+//                 by the share of K (1..64) hemisphere directions above the pixel centre's hit point that are
+//                 open within --ao-radius (esc_render_ambient, esc_modulate; one GPU, not with --ispc)
+//   --ao-radius R with --ao, required: how far a sample ray looks (finite, > 0)
+//   --ao-sets S   with --ao: S (1..64, default 16) sets of K cosine-weighted directions, one drawn per pixel
+//   --ao-bias B   with --ao: the sample rays start B (finite, >= 0; default 1e-4) off the surface
+//   --ao-seed N   with --ao: seed of the direction table and of the per-pixel draw (default 0)
 //   --help        print the options and leave
 #include <chrono>
 #include <cmath>
@@ -90,7 +97,29 @@ const char *kUsage =
     "  --bias X                   with --bounces: a bounce starts X off its surface (default 1e-4)\n"
     "  --refract                  with --bounces: transmissive materials (Tf / Ni) refract\n"
     "  --fresnel                  with --bounces: Schlick's term picks reflection or refraction per sample\n"
+    "  --ao K --ao-radius R       multiply the image by the visibility of K hemisphere directions within R\n"
+    "  --ao-sets S --ao-bias B --ao-seed N   with --ao: direction sets (16), surface offset (1e-4), seed (0)\n"
     "  --help                     this text\n";
+
+// --ao's values: a whole number in [lo, hi], or a finite float (> 0, or >= 0), with nothing after it
+long parse_whole(const char *flag, const char *next, long lo, long hi) {
+  if (!next) die(std::string(flag) + " needs a value");
+  char *end = nullptr;
+  const long v = std::strtol(next, &end, 10);
+  if (end == next || *end != '\0' || v < lo || v > hi)
+    die(std::string(flag) + " must be a whole number from " + std::to_string(lo) + " to " + std::to_string(hi) +
+        ", got " + next);
+  return v;
+}
+
+float parse_finite(const char *flag, const char *next, bool zero_ok) {
+  if (!next) die(std::string(flag) + " needs a value");
+  char *end = nullptr;
+  const float v = std::strtof(next, &end);
+  if (end == next || *end != '\0' || !std::isfinite(v) || !(zero_ok ? v >= 0.f : v > 0.f))
+    die(std::string(flag) + " must be a finite number " + (zero_ok ? ">= 0" : "> 0") + ", got " + next);
+  return v;
+}
 
 } // namespace
 
@@ -105,6 +134,10 @@ int main(int argc, char *argv[]) {
   bool have_adaptive = false;
   bool have_bias = false, refract = false, fresnel = false;
   unsigned long long seed = 0;
+  int ao = 0, ao_sets = 16;
+  float ao_radius = 0.f, ao_bias = 1e-4f;
+  unsigned long long ao_seed = 0;
+  bool have_ao_radius = false, have_ao_extra = false;
 
   for (int arg = 1; arg < argc; arg++) {
     const std::string a = argv[arg];
@@ -183,6 +216,34 @@ int main(int argc, char *argv[]) {
     }
     if (a == "--refract") { refract = true; continue; }
     if (a == "--fresnel") { fresnel = true; continue; }
+    if (a == "--ao") { ao = (int)parse_whole("--ao", next, 1, 64); arg++; continue; }
+    if (a == "--ao-radius") {
+      ao_radius = parse_finite("--ao-radius", next, false);
+      have_ao_radius = true;
+      arg++;
+      continue;
+    }
+    if (a == "--ao-sets") {
+      ao_sets = (int)parse_whole("--ao-sets", next, 1, 64);
+      have_ao_extra = true;
+      arg++;
+      continue;
+    }
+    if (a == "--ao-bias") {
+      ao_bias = parse_finite("--ao-bias", next, true);
+      have_ao_extra = true;
+      arg++;
+      continue;
+    }
+    if (a == "--ao-seed") {
+      if (!next) die("--ao-seed needs N");
+      char *end = nullptr;
+      ao_seed = std::strtoull(next, &end, 0);
+      if (end == next || *end != '\0') die(std::string("--ao-seed must be a whole number, got ") + next);
+      have_ao_extra = true;
+      arg++;
+      continue;
+    }
     if (a == "--help") {
       std::cout << kUsage;
       return 0;
@@ -201,6 +262,9 @@ int main(int argc, char *argv[]) {
   if (refract && fresnel) die("--refract and --fresnel exclude each other");
   if (refract && bounces < 0) die("--refract needs --bounces");
   if (fresnel && bounces < 0) die("--fresnel needs --bounces");
+  if (ao && !have_ao_radius) die("--ao needs --ao-radius");
+  if (!ao && (have_ao_radius || have_ao_extra)) die("--ao-radius, --ao-sets, --ao-bias and --ao-seed need --ao");
+  if (ao && (ispc || gpus != 1)) die("--ao renders on one GPU and not with --ispc");
 
   esc_scene *scene = esc_scene_new();
   if (!scene) die("out of memory");
@@ -326,6 +390,26 @@ int main(int argc, char *argv[]) {
     }
     if (debug >= 2)
       for (int i = 0; i < gpus; i++) std::cerr << " band " << i << " kernel ms: " << ms[i] << std::endl;
+  }
+  if (ao) {
+    // the frame back on the device, the pixel centres' visibility, the product in place, and home again
+    std::vector<float> table((size_t)ao_sets * ao * 3);
+    check(esc_ambient_cosine_table(ao_sets, ao, ao_seed, table.data()), "ambient table");
+    check(esc_set_ambient_table(ctx, ao_sets, ao, table.data()), "ambient table");
+    const esc_ambient_options ao_opts = {ao, ao_sets, ao_radius, ao_bias, ao_seed, 0u, 0u};
+    float *d_image = nullptr, *d_vis = nullptr;
+    if (hipMalloc((void **)&d_image, image.size() * sizeof(float)) != hipSuccess ||
+        hipMalloc((void **)&d_vis, (size_t)W * H * sizeof(float)) != hipSuccess)
+      die("out of device memory");
+    if (hipMemcpy(d_image, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+      die("copy to the device failed");
+    check(esc_render_ambient(ctx, &cam, W, H, &ao_opts, d_vis, nullptr), "ambient");
+    check(esc_modulate(ctx, (int64_t)W * H, d_image, d_vis, d_image, nullptr), "modulate");
+    check(esc_context_synchronize(ctx), "ambient");
+    if (hipMemcpy(image.data(), d_image, image.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+      die("copy back failed");
+    (void)hipFree(d_image);
+    (void)hipFree(d_vis);
   }
   auto end_time = std::chrono::high_resolution_clock::now();
 

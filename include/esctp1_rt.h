@@ -791,6 +791,86 @@ typedef struct esc_transmit_stats {
 /* synchronises the context's stream, like esc_last_trace_stats */
 int esc_last_transmit_stats(esc_context *ctx, esc_transmit_stats *out);
 
+/* ---- ambient occlusion: hemisphere visibility of rays and frames (rt_ambient.hip, DESIGN.md section
+ * 3.17) ----
+ * An extension beyond the reference, whose ambient term is the constant ka * 0.5: how many of K directions
+ * of the hemisphere above a ray's hit point are open within a radius.  The result is an integer count per
+ * ray.  All arithmetic is fp32 with one rounding per written operation, no contraction, vec.h's operation
+ * order for dot, normalize, vector +- and vector * scalar, and consists of + - * / and sqrt only: the
+ * sample directions are DATA, a table the caller supplies.
+ *
+ * The table: S sets x K samples x 3 floats (1 <= S, K <= 64), local directions about +z, row-major
+ * (table[set][k] at 3*(set*K + k)).  Its contents are never validated.  esc_set_ambient_table copies it
+ * from HOST memory to the device; it belongs to the context and survives scene uploads (a new table
+ * replaces it).  esc_ambient_cosine_table fills one on the host, without a context, with cosine-weighted
+ * unit vectors (z > 0): deterministic in (sets, samples, seed), drawn with the host's libm -- the result
+ * is data that a caller can read back, store or replace.
+ *
+ * For ray i with origin o and direction d (used as given), K = opts.samples, S = opts.sets (the first K
+ * samples of the first S sets of the context's table: each at most the table's own):
+ *
+ *   1. (t, id) = the closest hit esc_intersect_rays finds with bound FLT_MAX.  A miss: count = K.
+ *   2. N = the normal esc_shade_rays computes (main.cpp:723-738 incl. quirk S1, u = 0; a sphere:
+ *      normalize((o + d*t) - C))
+ *   3. sn = dot(d, N);  Nf = (sn > 0) ? -N : N;  P = (o + d*t) + Nf*bias         (esc_trace_rays' bounce origin)
+ *   4. sg = copysign(1, Nf.z);  a = -1 / (sg + Nf.z);  b = (Nf.x*Nf.y)*a          (|sg + Nf.z| >= 1)
+ *      T = (1 + (sg*(Nf.x*Nf.x))*a,  sg*b,  -(sg*Nf.x))
+ *      B = (b,  sg + (Nf.y*Nf.y)*a,  -Nf.y)
+ *   5. set = mix(opts.seed, pixel_base + i mod 2^32, 0xFFFFFFFE) mod S            (mix: see esc_trace_options;
+ *      no light has index 0xFFFFFFFE and the Fresnel draw uses 0xFFFFFFFF, so the three draws are independent)
+ *   6. for k = 0 .. K-1:  l = table[set][k];  w = normalize((T*l.x + B*l.y) + Nf*l.z)
+ *      sample k is open iff esc_occluded_rays(P, w, tmax = radius) is 0;  count = the open samples
+ *   7. vis = float(count) / float(K)                                              (a miss: 1.0f)
+ *
+ * A sample ray is an ordinary ray to the sweeps: the reference's normalize() leaves w within precondition
+ * (c) of the filtered sweep, and a ray outside the preconditions runs the reference loop in index order.
+ * With bias == 0 a sample may meet its own surface at t ~ 0, decided by the reference's own rounding
+ * (esc_trace_rays says the same of its bounces); bias is the remedy.
+ *
+ * radius: finite and > 0, FLT_MAX = unbounded.  bias: finite and >= 0.  flags: 0 or ESC_RENDER_EXACT_ONLY
+ * (every primary and sample ray through the index-order loop).  Anything else, samples or sets outside
+ * 1 .. the table's, or a call before esc_set_ambient_table is ESC_ERR_INVALID.  Pointer, alignment and
+ * n == 0 rules are esc_shade_rays'; the calls are asynchronous on the context's stream and read only
+ * per-scene tables and the sample table. */
+typedef struct esc_ambient_options {
+  int32_t samples;     /* K */
+  int32_t sets;        /* S */
+  float radius;
+  float bias;
+  uint64_t seed;
+  uint32_t pixel_base; /* esc_ambient_rays: the hash's pixel of ray 0; esc_render_ambient ignores it */
+  uint32_t flags;
+} esc_ambient_options;
+/* counts of the last esc_ambient_rays / esc_render_ambient call (zero before the first) */
+typedef struct esc_ambient_stats {
+  uint64_t rays;
+  uint64_t hit_rays;         /* rays whose closest hit found a primitive */
+  uint64_t samples;          /* sample rays: K * hit_rays */
+  uint64_t occluded_samples; /* sample rays that met a primitive within the radius */
+  uint64_t exact_rays;       /* primary or sample rays that took the index-order reference loop */
+  uint64_t exact_tests;      /* (ray, primitive) pairs that ran the reference arithmetic */
+} esc_ambient_stats;
+/* host_table: sets * samples * 3 floats in HOST memory; synchronises the context's stream */
+int esc_set_ambient_table(esc_context *ctx, int32_t sets, int32_t samples, const float *host_table);
+/* out: sets * samples * 3 floats in host memory; needs no context and no device */
+int esc_ambient_cosine_table(int32_t sets, int32_t samples, uint64_t seed, float *out);
+/* d_vis (n floats, required) receives vis; d_count (n int32), d_t, d_geom, d_prim (each NULL or n) the
+ * count and what esc_intersect_rays gives for the same ray */
+int esc_ambient_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs,
+                     const esc_ambient_options *opts, float *d_vis, int32_t *d_count, float *d_t,
+                     int32_t *d_geom, int32_t *d_prim);
+/* ray i = h*W + w is ray i of esc_camera_rays(cam, W, H, 0, H, NULL), made inside the kernel, with pixel id
+ * i (pixel_base 0): bit for bit esc_ambient_rays on those rays.  d_vis: W*H floats, d_count: W*H or NULL.
+ * W, H and cam follow esc_render_supersampled. */
+int esc_render_ambient(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
+                       const esc_ambient_options *opts, float *d_vis, int32_t *d_count);
+/* d_out[3i + c] = fl(d_rgb[3i + c] * d_vis[i]) for n pixels, and d_out8 = its quantisation
+ * (main.cpp:676-682).  d_out may be d_rgb itself; d_out or d_out8 may be NULL, not both.  Asynchronous. */
+int esc_modulate(esc_context *ctx, int64_t n, const float *d_rgb, const float *d_vis, float *d_out,
+                 uint8_t *d_out8);
+/* synchronises the context's stream */
+int esc_last_ambient_stats(esc_context *ctx, esc_ambient_stats *out);
+
 /* Whole frame into HOST memory, synchronous: render + D2H.  `image` = W*H*3 floats. */
 int esc_render_frame_host(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
                           const esc_render_options *opts, float *image, uint8_t *rgb8);
