@@ -18,7 +18,7 @@ from ._capi import (ESC_FACE_FIXED, ESC_FACE_HASH, ESC_STAGE_AUTO, ESC_STAGE_BVH
                     ESC_STAGE_SMEM, ESC_TRANSMIT_OFF, ESC_TRANSMIT_REFRACT, ESC_TRANSMIT_FRESNEL, EscError,
                     check)
 
-__all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table",
+__all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table", "environment_sky", "environment_lookup_host",
            "EscError", "ESC_FACE_FIXED", "ESC_FACE_HASH", "ESC_STAGE_AUTO", "ESC_STAGE_SMEM",
            "ESC_STAGE_LDS", "ESC_STAGE_BVH", "ESC_RENDER_EXACT_ONLY", "ESC_RENDER_TIME_KERNELS", "ESC_RENDER_INDEX_ORDER", "ESC_RENDER_SHADE_QUEUE",
            "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "ESC_TRANSMIT_OFF", "ESC_TRANSMIT_REFRACT", "ESC_TRANSMIT_FRESNEL", "version"]
@@ -267,6 +267,29 @@ def ambient_table(sets, samples, seed=0):
     or any other array of local directions of that shape."""
     out = np.zeros((int(sets), int(samples), 3), np.float32) if sets > 0 and samples > 0 else np.zeros(3, np.float32)
     check(_capi.load().esc_ambient_cosine_table(int(sets), int(samples), int(seed) & (2 ** 64 - 1), _fp(out)))
+    return out
+
+
+def environment_sky(res, zenith, horizon, ground):
+    """esc_environment_sky: a vertical gradient (zenith above, horizon, ground below) as an environment cube,
+    (6, res, res, 3) float32, made on the host (no GPU needed) in double arithmetic without transcendentals.
+    Renderer.set_environment takes it, or any other array of that shape."""
+    res = int(res)
+    out = np.zeros((6, res, res, 3), np.float32) if 1 <= res <= 1024 else np.zeros(3, np.float32)
+    check(_capi.load().esc_environment_sky(res, _fp(_f32(zenith, (3,))), _fp(_f32(horizon, (3,))),
+                                           _fp(_f32(ground, (3,))), _fp(out)))
+    return out
+
+
+def environment_lookup_host(cube, dirs):
+    """esc_environment_lookup_host: env(d) of include/esctp1_rt.h for numpy directions (n, 3) on the host, by
+    the code the kernels run.  cube: (6, R, R, 3) float32.  -> (n, 3) float32"""
+    t = np.ascontiguousarray(cube, dtype=np.float32)
+    if t.ndim != 4 or t.shape[0] != 6 or t.shape[1] != t.shape[2] or t.shape[3] != 3:
+        raise ValueError("cube must have shape (6, R, R, 3)")
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros_like(d)
+    check(_capi.load().esc_environment_lookup_host(t.shape[1], _fp(t), d.shape[0], _fp(d), _fp(out)))
     return out
 
 
@@ -753,6 +776,53 @@ class Renderer:
         check(self._lib.esc_last_ambient_stats(self._h, C.byref(s)))
         return {k: int(getattr(s, k)) for k in ("rays", "hit_rays", "samples", "occluded_samples", "exact_rays",
                                                 "exact_tests")}
+
+    # ---- environment cube map (esc_set_environment / esc_environment_rays) ------------------------------
+    def set_environment(self, cube):
+        """esc_set_environment: cube is a (6, R, R, 3) float32 array, faces +x, -x, +y, -y, +z, -z
+        (environment_sky makes a gradient), 1 <= R <= 1024, or None to remove the environment.  While one is
+        set, the rays of trace_rays / trace / render_traced that miss take its colour instead of black, at
+        every level; nothing else changes.  It belongs to the renderer and survives uploads.  Synchronises."""
+        if cube is None:
+            check(self._lib.esc_set_environment(self._h, 0, None))
+            return
+        t = np.ascontiguousarray(cube, dtype=np.float32)
+        if t.ndim != 4 or t.shape[0] != 6 or t.shape[1] != t.shape[2] or t.shape[3] != 3:
+            raise ValueError("cube must have shape (6, R, R, 3)")
+        check(self._lib.esc_set_environment(self._h, t.shape[1], _fp(t)))
+
+    @property
+    def environment_res(self):
+        """R of the renderer's environment cube, 0 when none is set"""
+        r = C.c_int32(-1)
+        check(self._lib.esc_get_environment_res(self._h, C.byref(r)))
+        return int(r.value)
+
+    def environment_rays(self, dirs, rgb, rgb8=None):
+        """env(d) of n directions (esc_environment_rays), asynchronous on the renderer's stream.  Contiguous
+        device tensors: dirs (n, 3) float32; outputs rgb (n, 3) float32 or None, rgb8 (n, 3) uint8 or None
+        (not both None).  Needs an environment, no scene."""
+        import torch
+        if not hasattr(dirs, "shape") or len(dirs.shape) != 2:
+            raise ValueError("dirs must have shape (n, 3)")
+        n = int(dirs.shape[0])
+        pd = self._query_ptr("dirs", dirs, torch.float32, (n, 3))
+        check(self._lib.esc_environment_rays(
+            self._h, n, pd, None if rgb is None else self._query_ptr("rgb", rgb, torch.float32, (n, 3)),
+            None if rgb8 is None else self._query_ptr("rgb8", rgb8, torch.uint8, (n, 3))))
+
+    def environment(self, dirs):
+        """Synchronous lookup of numpy directions: {"rgb", "rgb8"} as numpy arrays."""
+        import torch
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        dev = torch.device("cuda", self.device)
+        td = torch.from_numpy(d).to(dev)
+        rgb = torch.empty((d.shape[0], 3), dtype=torch.float32, device=dev)
+        rgb8 = torch.empty((d.shape[0], 3), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the copy ran on torch's stream
+        self.environment_rays(td, rgb, rgb8)
+        self.synchronize()
+        return {"rgb": rgb.cpu().numpy(), "rgb8": rgb8.cpu().numpy()}
 
     def trace_rays(self, origins, dirs, rgb, *, max_depth, bias, rgb8=None, pixel_base=0, shadows=True,
                    face_mode=ESC_FACE_FIXED, fixed_face=0, seed=0, exact=False, transmission="off"):

@@ -257,6 +257,11 @@ SIGNATURES = {
                                      C.POINTER(esc_ambient_options), _P, _P]),
     "esc_modulate": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
     "esc_last_ambient_stats": (C.c_int, [_P, C.POINTER(esc_ambient_stats)]),
+    "esc_set_environment": (C.c_int, [_P, C.c_int32, _F]),
+    "esc_get_environment_res": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "esc_environment_sky": (C.c_int, [C.c_int32, _F, _F, _F, _F]),
+    "esc_environment_rays": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    "esc_environment_lookup_host": (C.c_int, [C.c_int32, _F, C.c_int64, _F, _F]),
     "esc_render_frame_host": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
                                         C.POINTER(esc_render_options), _F, _U8]),
     "esc_render_frame_multi": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,

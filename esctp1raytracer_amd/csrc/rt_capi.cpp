@@ -18,6 +18,7 @@
 #include "../host/scene_tables.h"
 #include "rt_adaptive.h"
 #include "rt_ambient.h"
+#include "rt_environ.h"
 #include "rt_device.h"
 #include "rt_query.h"
 #include "rt_shade_rays.h"
@@ -58,6 +59,7 @@ extern "C" int esc_launch_adaptive_mask(const esc::AdaptiveMaskParams *p, hipStr
 extern "C" int esc_launch_adaptive_list(const esc::AdaptiveListParams *p, hipStream_t stream);
 extern "C" int esc_launch_adaptive_refine(const esc::AdaptiveRefineParams *p, hipStream_t stream);
 extern "C" int esc_launch_ambient(const esc::AmbientParams *p, int camera, hipStream_t stream);
+extern "C" int esc_launch_environment_rays(const esc::EnvRaysParams *p, hipStream_t stream);
 extern "C" int esc_launch_modulate(const esc::ModulateParams *p, hipStream_t stream);
 extern "C" int esc_launch_assemble(const void *gathered, void *frame, size_t rank_pitch_bytes,
                                    int n_ranks, int H, int strip_rows, size_t row_bytes,
@@ -200,6 +202,10 @@ struct esc_context {
   int32_t am_sets = 0, am_samples = 0;
   unsigned long long *d_amstats = nullptr;
   int32_t am_k = 0;
+  // the environment cube of esc_set_environment (rt_environ.h): 6 * env_res^2 records of 16 bytes; the
+  // context's, not the scene's.  nullptr: traced rays that miss stay black
+  esc::EnvTexel *d_env = nullptr;
+  int32_t env_res = 0;
 };
 
 namespace {
@@ -502,7 +508,7 @@ void esc_context_destroy(esc_context *ctx) {
                   ctx->d_tri_boxes, ctx->d_sph_boxes, ctx->d_bin_hdr, ctx->d_bin_tri_ids,
                   ctx->d_bin_sph_ids, ctx->lbins.face_hdr, ctx->lbins.counts, ctx->lbins.tri_ids,
                   ctx->lbins.sph_ids, ctx->d_qstats, ctx->d_sstats, ctx->d_ss, ctx->d_tstats, ctx->d_tr,
-                  ctx->d_transmit, ctx->d_astats, ctx->d_ad, ctx->d_am_table, ctx->d_amstats};
+                  ctx->d_transmit, ctx->d_astats, ctx->d_ad, ctx->d_am_table, ctx->d_amstats, ctx->d_env};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t ev : ctx->ev)
@@ -2111,6 +2117,8 @@ static int trace_launch(esc_context *ctx, const char *fn, int64_t n, const float
     p.transmit = ctx->d_transmit;
     p.transmit_mode = transmission;
   }
+  p.env.texels = ctx->d_env; // null: the kernels without the lookup
+  p.env.res = ctx->env_res;
   float *queue[2] = {d_queues, d_queues + (size_t)esc::kTraceQueuePlanes * (size_t)n};
   for (int k = 0; k <= max_depth; ++k) {
     p.level = k;
@@ -2311,6 +2319,146 @@ int esc_render_traced_ex(esc_context *ctx, const esc_camera *cam, int32_t W, int
   if (rc) return rc;
   return render_traced_impl(fn, ctx, cam, W, H, spp, topts->max_depth, topts->bias, topts->transmission, opts,
                             d_image, d_u8);
+}
+
+// ---- environment cube map (rt_environ.h, rt_environ.hip) -------------------------------------------
+// texels[face][j][i][3] -> one 16-byte record per texel, the layout the kernels read
+static void env_repack(int32_t res, const float *texels, std::vector<esc::EnvTexel> &out) {
+  const size_t n = (size_t)6 * (size_t)res * (size_t)res;
+  out.resize(n);
+  for (size_t k = 0; k < n; ++k) out[k] = esc::EnvTexel{texels[3 * k], texels[3 * k + 1], texels[3 * k + 2], 0.f};
+}
+
+int esc_set_environment(esc_context *ctx, int32_t res, const float *host_texels) {
+  const char *fn = "esc_set_environment";
+  if (!ctx) {
+    set_error(std::string(fn) + ": ctx is null");
+    return ESC_ERR_INVALID;
+  }
+  if (res < 0 || res > esc::kEnvMaxRes) {
+    set_error(std::string(fn) + ": res must be in 0..1024");
+    return ESC_ERR_INVALID;
+  }
+  if ((res == 0) != (host_texels == nullptr)) {
+    set_error(std::string(fn) + ": res == 0 goes with host_texels == NULL (no environment), and only with it");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream)); // a call in flight may still read the old cube
+  if (ctx->d_env) HIP_TRY(hipFree(ctx->d_env));
+  ctx->d_env = nullptr;
+  ctx->env_res = 0;
+  if (res == 0) return ESC_OK;
+  std::vector<esc::EnvTexel> packed;
+  env_repack(res, host_texels, packed);
+  const size_t bytes = packed.size() * sizeof(esc::EnvTexel);
+  HIP_TRY(hipMalloc((void **)&ctx->d_env, bytes));
+  HIP_TRY(hipMemcpyAsync(ctx->d_env, packed.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream)); // `packed` goes out of scope
+  ctx->env_res = res;
+  return ESC_OK;
+}
+
+int esc_get_environment_res(esc_context *ctx, int32_t *res) {
+  if (!ctx || !res) {
+    set_error(!ctx ? "esc_get_environment_res: ctx is null" : "esc_get_environment_res: res is null");
+    return ESC_ERR_INVALID;
+  }
+  *res = ctx->env_res;
+  return ESC_OK;
+}
+
+int esc_environment_sky(int32_t res, const float zenith[3], const float horizon[3], const float ground[3],
+                        float *out) {
+  const char *fn = "esc_environment_sky";
+  if (res < 1 || res > esc::kEnvMaxRes) {
+    set_error(std::string(fn) + ": res must be in 1..1024");
+    return ESC_ERR_INVALID;
+  }
+  if (!zenith || !horizon || !ground || !out) {
+    set_error(std::string(fn) + ": zenith, horizon, ground and out are required");
+    return ESC_ERR_INVALID;
+  }
+  const double R = (double)res;
+  for (int face = 0; face < 6; ++face) {
+    const int axis = face / 2;
+    for (int j = 0; j < res; ++j)
+      for (int i = 0; i < res; ++i) {
+        double D[3];
+        D[axis] = (face & 1) ? -1.0 : 1.0;
+        D[(axis + 1) % 3] = (((double)i + 0.5) / R) * 2.0 - 1.0;
+        D[(axis + 2) % 3] = (((double)j + 0.5) / R) * 2.0 - 1.0;
+        const double e = D[1] / std::sqrt((D[0] * D[0] + D[1] * D[1]) + D[2] * D[2]);
+        float *o = out + 3 * (((size_t)face * res + j) * res + i);
+        for (int c = 0; c < 3; ++c) {
+          const double h = (double)horizon[c];
+          o[c] = (float)(e >= 0.0 ? h + ((double)zenith[c] - h) * e : h + ((double)ground[c] - h) * (-e));
+        }
+      }
+  }
+  return ESC_OK;
+}
+
+int esc_environment_rays(esc_context *ctx, int64_t n, const float *d_dirs, float *d_rgb, uint8_t *d_rgb8) {
+  const std::string fn("esc_environment_rays");
+  if (!ctx) {
+    set_error(fn + ": ctx is null");
+    return ESC_ERR_INVALID;
+  }
+  if (!ctx->d_env) {
+    set_error(fn + ": no environment (esc_set_environment)");
+    return ESC_ERR_INVALID;
+  }
+  if (n < 0) {
+    set_error(fn + ": n < 0");
+    return ESC_ERR_INVALID;
+  }
+  if (n > 0 && (!d_dirs || (!d_rgb && !d_rgb8))) {
+    set_error(fn + ": d_dirs and one of d_rgb, d_rgb8 are required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_dirs | (uintptr_t)d_rgb) & 3u) {
+    set_error(fn + ": device pointers must be 4-byte aligned (d_rgb8 excepted)");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error(fn + ": n exceeds one launch (2^32 - 1 workgroups of 256 directions)");
+    return ESC_ERR_INVALID;
+  }
+  if (n == 0) return ESC_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  esc::EnvRaysParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.env.texels = ctx->d_env;
+  p.env.res = ctx->env_res;
+  p.n = n;
+  p.dirs = d_dirs;
+  p.rgb = d_rgb;
+  p.rgb8 = d_rgb8;
+  const int e = esc_launch_environment_rays(&p, ctx->stream);
+  if (e) {
+    set_error(fn + ": k_environment_rays launch: " + hipGetErrorString((hipError_t)e));
+    return ESC_ERR_HIP;
+  }
+  return ESC_OK;
+}
+
+int esc_environment_lookup_host(int32_t res, const float *texels, int64_t n, const float *dirs, float *rgb) {
+  const char *fn = "esc_environment_lookup_host";
+  if (res < 1 || res > esc::kEnvMaxRes) {
+    set_error(std::string(fn) + ": res must be in 1..1024");
+    return ESC_ERR_INVALID;
+  }
+  if (n < 0 || !texels || (n > 0 && (!dirs || !rgb))) {
+    set_error(std::string(fn) + ": n >= 0, texels, dirs and rgb are required");
+    return ESC_ERR_INVALID;
+  }
+  std::vector<esc::EnvTexel> packed; // the records the kernels read, and rt_environ.h's code on them
+  env_repack(res, texels, packed);
+  for (int64_t i = 0; i < n; ++i)
+    esc::env_lookup(packed.data(), res, dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], rgb[3 * i], rgb[3 * i + 1],
+                    rgb[3 * i + 2]);
+  return ESC_OK;
 }
 
 // ---- ambient occlusion (rt_ambient.hip) ------------------------------------------------------------

@@ -3,6 +3,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "rt_environ.h"
 #include "rt_shade_rays.h"
 
 namespace esc {
@@ -31,6 +32,9 @@ struct TraceParams {
   const float *transmit;
   int32_t transmit_mode;
   int32_t pad2;
+  // k_trace<*, *, *, true> only, and at the end for the same reason: the context's environment cube
+  // (esc_set_environment); texels == nullptr selects the kernels without the lookup
+  EnvParams env;
 };
 
 } // namespace esc

@@ -29,7 +29,9 @@ namespace esc {
 // nothing of the ray outlives the light loop, and the kernel is k_shade_rays plus the update of C.
 // TRANSMIT: the scene has a transmissive material and the call asked for refraction (rt_transmit.h);
 // every other call runs the <*, *, false> instantiations, which are the mirror-only kernels unchanged.
-template <bool FIRST, bool LAST, bool TRANSMIT>
+// ENV: the context holds an environment cube (rt_environ.h): a ray that misses takes the colour env(d)
+// instead of black.  Without one the <*, *, *, false> instantiations run, the kernels as they were.
+template <bool FIRST, bool LAST, bool TRANSMIT, bool ENV>
 __global__ __launch_bounds__(256) void k_trace(const TraceParams T) {
   const ShadeParams &P = T.s;
   const QueryParams &p = P.q;
@@ -64,6 +66,10 @@ __global__ __launch_bounds__(256) void k_trace(const TraceParams T) {
 #include "rt_shade_body.inc"
 #undef SHADE_BODY_PIXEL
 #undef SHADE_BODY_SEED
+
+  if constexpr (ENV) { // lanes that hit are masked off, and a wave without a miss skips the loads
+    if (valid && !has_hit) env_lookup(T.env.texels, T.env.res, d.x, d.y, d.z, r, g, b);
+  }
 
   if (valid) {
     float *C = P.rgb + 3 * (int64_t)dest;
@@ -171,17 +177,26 @@ extern "C" int esc_launch_trace_level(const esc::TraceParams *p, hipStream_t str
   const bool first = p->level == 0, last = p->level == p->max_depth;
   // a last level never bounces: <*, true, true> would be <*, true, false>
   const bool transmit = p->transmit != nullptr && p->transmit_mode != esc::kTransmitOff && !last;
+  const bool env = p->env.texels != nullptr;
+#define TRACE_LAUNCH(F, L, X)                                                                                   \
+  do {                                                                                                          \
+    if (env)                                                                                                    \
+      hipLaunchKernelGGL((esc::k_trace<F, L, X, true>), grid, dim3(256), 0, stream, *p);                        \
+    else                                                                                                        \
+      hipLaunchKernelGGL((esc::k_trace<F, L, X, false>), grid, dim3(256), 0, stream, *p);                       \
+  } while (0)
   if (first && last)
-    hipLaunchKernelGGL((esc::k_trace<true, true, false>), grid, dim3(256), 0, stream, *p);
+    TRACE_LAUNCH(true, true, false);
   else if (last)
-    hipLaunchKernelGGL((esc::k_trace<false, true, false>), grid, dim3(256), 0, stream, *p);
+    TRACE_LAUNCH(false, true, false);
   else if (first && transmit)
-    hipLaunchKernelGGL((esc::k_trace<true, false, true>), grid, dim3(256), 0, stream, *p);
+    TRACE_LAUNCH(true, false, true);
   else if (first)
-    hipLaunchKernelGGL((esc::k_trace<true, false, false>), grid, dim3(256), 0, stream, *p);
+    TRACE_LAUNCH(true, false, false);
   else if (transmit)
-    hipLaunchKernelGGL((esc::k_trace<false, false, true>), grid, dim3(256), 0, stream, *p);
+    TRACE_LAUNCH(false, false, true);
   else
-    hipLaunchKernelGGL((esc::k_trace<false, false, false>), grid, dim3(256), 0, stream, *p);
+    TRACE_LAUNCH(false, false, false);
+#undef TRACE_LAUNCH
   return (int)hipGetLastError();
 }

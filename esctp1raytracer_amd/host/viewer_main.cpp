@@ -48,6 +48,11 @@
 //   --ao-sets S   with --ao: S (1..64, default 16) sets of K cosine-weighted directions, one drawn per pixel
 //   --ao-bias B   with --ao: the sample rays start B (finite, >= 0; default 1e-4) off the surface
 //   --ao-seed N   with --ao: seed of the direction table and of the per-pixel draw (default 0)
+//   --sky Z/H/G   environment: a vertical gradient (zenith, horizon, ground colours, each r,g,b; finite) that
+//                 the rays which leave the scene see, primary rays and bounces alike (esc_environment_sky,
+//                 esc_set_environment).  The frame is rendered through esc_render_traced_ex, at depth 0 when
+//                 --bounces is absent (one GPU, not with --ispc, --bvh, --bvh-tree or --adaptive)
+//   --sky-res N   with --sky: texels per side of the cube (1..1024, default 64)
 //   --help        print the options and leave
 #include <chrono>
 #include <cmath>
@@ -99,6 +104,8 @@ const char *kUsage =
     "  --fresnel                  with --bounces: Schlick's term picks reflection or refraction per sample\n"
     "  --ao K --ao-radius R       multiply the image by the visibility of K hemisphere directions within R\n"
     "  --ao-sets S --ao-bias B --ao-seed N   with --ao: direction sets (16), surface offset (1e-4), seed (0)\n"
+    "  --sky zr,zg,zb/hr,hg,hb/gr,gg,gb   rays that leave the scene see a zenith / horizon / ground gradient\n"
+    "  --sky-res N                with --sky: texels per side of the environment cube (1..1024, default 64)\n"
     "  --help                     this text\n";
 
 // --ao's values: a whole number in [lo, hi], or a finite float (> 0, or >= 0), with nothing after it
@@ -121,6 +128,22 @@ float parse_finite(const char *flag, const char *next, bool zero_ok) {
   return v;
 }
 
+// --sky's value: three colours separated by '/', each three finite numbers separated by ','
+void parse_sky(const char *next, float out[9]) {
+  const std::string err = "--sky needs zr,zg,zb/hr,hg,hb/gr,gg,gb with nine finite numbers";
+  if (!next) die(err);
+  const char *p = next;
+  for (int k = 0; k < 9; ++k) {
+    char *end = nullptr;
+    const float v = std::strtof(p, &end);
+    if (end == p || !std::isfinite(v)) die(err + ", got " + next);
+    out[k] = v;
+    const char want = k == 8 ? '\0' : (k % 3 == 2 ? '/' : ',');
+    if (*end != want) die(err + ", got " + next);
+    p = end + 1;
+  }
+}
+
 } // namespace
 
 int main(int argc, char *argv[]) {
@@ -138,6 +161,9 @@ int main(int argc, char *argv[]) {
   float ao_radius = 0.f, ao_bias = 1e-4f;
   unsigned long long ao_seed = 0;
   bool have_ao_radius = false, have_ao_extra = false;
+  bool sky = false, have_sky_res = false;
+  float sky_colours[9] = {0};
+  int sky_res = 64;
 
   for (int arg = 1; arg < argc; arg++) {
     const std::string a = argv[arg];
@@ -244,6 +270,13 @@ int main(int argc, char *argv[]) {
       arg++;
       continue;
     }
+    if (a == "--sky") { parse_sky(next, sky_colours); sky = true; arg++; continue; }
+    if (a == "--sky-res") {
+      sky_res = (int)parse_whole("--sky-res", next, 1, ESC_ENV_MAX_RES);
+      have_sky_res = true;
+      arg++;
+      continue;
+    }
     if (a == "--help") {
       std::cout << kUsage;
       return 0;
@@ -265,6 +298,9 @@ int main(int argc, char *argv[]) {
   if (ao && !have_ao_radius) die("--ao needs --ao-radius");
   if (!ao && (have_ao_radius || have_ao_extra)) die("--ao-radius, --ao-sets, --ao-bias and --ao-seed need --ao");
   if (ao && (ispc || gpus != 1)) die("--ao renders on one GPU and not with --ispc");
+  if (have_sky_res && !sky) die("--sky-res needs --sky");
+  if (sky && (ispc || flat || gpus != 1)) die("--sky renders on one GPU and not with --ispc, --bvh or --bvh-tree");
+  if (sky && have_adaptive) die("--sky is seen by traced frames: not with --adaptive");
 
   esc_scene *scene = esc_scene_new();
   if (!scene) die("out of memory");
@@ -349,14 +385,22 @@ int main(int argc, char *argv[]) {
                 << "\n num_light_faces = " << nlt << std::endl;
     trace(W, H, &icam, nt, tris, nl, lights, nlt, ltris, image.data(), debug, 0);
     esc_flat_free(fs);
-  } else if (ctx && (spp || bounces >= 0)) {
+  } else if (ctx && (spp || bounces >= 0 || sky)) {
     // device framebuffer of esc_render_supersampled / esc_render_traced, copied back like
     // esc_render_frame_host's
     esc_render_options so = opts;
     so.flags = 0;
     float *d_image = nullptr;
     if (hipMalloc((void **)&d_image, image.size() * sizeof(float)) != hipSuccess) die("out of device memory");
-    if (bounces >= 0 && (refract || fresnel)) {
+    if (sky) {
+      std::vector<float> cube((size_t)6 * sky_res * sky_res * 3);
+      check(esc_environment_sky(sky_res, sky_colours, sky_colours + 3, sky_colours + 6, cube.data()), "sky");
+      check(esc_set_environment(ctx, sky_res, cube.data()), "sky");
+      const esc_trace_options to = {bounces >= 0 ? bounces : 0, bias,
+                                    refract ? ESC_TRANSMIT_REFRACT : fresnel ? ESC_TRANSMIT_FRESNEL : ESC_TRANSMIT_OFF,
+                                    0};
+      check(esc_render_traced_ex(ctx, &cam, W, H, spp ? spp : 1, &so, &to, d_image, nullptr), "render");
+    } else if (bounces >= 0 && (refract || fresnel)) {
       const esc_trace_options to = {bounces, bias, refract ? ESC_TRANSMIT_REFRACT : ESC_TRANSMIT_FRESNEL, 0};
       check(esc_render_traced_ex(ctx, &cam, W, H, spp ? spp : 1, &so, &to, d_image, nullptr), "render");
     } else if (bounces >= 0)

@@ -697,7 +697,8 @@ int esc_last_adaptive_stats(esc_context *ctx, esc_adaptive_stats *out);
  * ordinary ray to the sweeps: it passes the precondition gate of the queries or runs the reference
  * loop in index order.  With bias == 0 a bounce may hit its own surface again at t ~ 0; that is
  * defined behaviour (the reference's shadow rays have the same property) and bias is the remedy.
- * max_depth == 0 is esc_shade_rays, bit for bit.
+ * max_depth == 0 is esc_shade_rays, bit for bit (while the context holds no environment: see
+ * esc_set_environment, which gives the rays that miss a colour at every level, level 0 included).
  *
  * Pointer, alignment, n == 0, flag and stage rules are esc_shade_rays'; ESC_RENDER_EXACT_ONLY sends
  * every primary, bounce and shadow ray through the index-order loop.  max_depth outside 0..16 or a
@@ -720,7 +721,7 @@ int esc_trace_rays(esc_context *ctx, int64_t n, const float *d_origins, const fl
                    const esc_render_options *opts, int32_t max_depth, float bias, float *d_rgb, uint8_t *d_rgb8);
 /* camera rays -> the loop above -> the accumulate / finish of esc_render_supersampled (same spp
  * rules, sample offsets and pixel ids), in row bands under the 256 MB scratch cap, queues included.
- * max_depth == 0 is esc_render_supersampled, bit for bit. */
+ * max_depth == 0 is esc_render_supersampled, bit for bit (while the context holds no environment). */
 int esc_render_traced(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
                       int32_t max_depth, float bias, const esc_render_options *opts, float *d_image,
                       uint8_t *d_u8);
@@ -870,6 +871,75 @@ int esc_modulate(esc_context *ctx, int64_t n, const float *d_rgb, const float *d
                  uint8_t *d_out8);
 /* synchronises the context's stream */
 int esc_last_ambient_stats(esc_context *ctx, esc_ambient_stats *out);
+
+/* ---- environment cube map: traced rays that miss see a sky (rt_environ.h, rt_environ.hip, rt_trace.hip,
+ * DESIGN.md section 3.18) ----
+ * An extension beyond the reference, whose framebuffer is black where nothing is hit.  The texels are DATA
+ * the caller supplies, like the ambient table; the lookup consists of + - * /, floor and compares only, so
+ * it is comparable bit for bit: a cube map and not a latitude / longitude map, no atan2 / acos runs anywhere.
+ *
+ * The cube: R texels per side, 1 <= R <= ESC_ENV_MAX_RES.  Host layout texels[face][j][i][3] floats,
+ * row-major (texel (face, j, i) at 3*((face*R + j)*R + i)); face order +x, -x, +y, -y, +z, -z, so
+ * face = 2*axis + (negative ? 1 : 0).  Its contents are never validated.
+ *
+ * The lookup env(d) for a direction d, used as given (it need not be of unit length).  All arithmetic fp32,
+ * one rounding per written operation, no contraction:
+ *
+ *   ax = |d.x|, ay = |d.y|, az = |d.z|
+ *   axis = 0 if (ax >= ay && ax >= az) else 1 if (ay >= az) else 2        (comparisons with NaN are false)
+ *   m = |d[axis]|;  a = d[(axis+1) % 3];  b = d[(axis+2) % 3];  negative = d[axis] < 0
+ *   env(d) = (0, 0, 0)  unless no component of d is NaN and 0 < m <= FLT_MAX
+ *   u = a / m;  v = b / m                                         (both in [-1, 1]; no mirroring per face)
+ *   x = ((u * 0.5f + 0.5f) * float(R)) - 0.5f;   x0 = floorf(x);  fx = x - x0
+ *   i0 = clamp(int(x0), 0, R-1);  i1 = clamp(int(x0) + 1, 0, R-1)       (the same for y from v: j0, j1, fy)
+ *   per channel, t = the face's texels:
+ *       c0 = t[j0][i0] + (t[j0][i1] - t[j0][i0]) * fx
+ *       c1 = t[j1][i0] + (t[j1][i1] - t[j1][i0]) * fx
+ *       env = c0 + (c1 - c0) * fy
+ *
+ * Bilinear inside a face and clamped at the face border; NO filtering across faces: a discontinuity of up
+ * to half a texel's gradient at a seam is the documented price.  R == 1 is one colour per face.  A constant
+ * cube returns its colour exactly.  x lies in [-0.5, R - 0.5] and fx in [0, 1]: fx rounds to 1 only for an x
+ * just under 0, where both indices are clamped to 0.
+ *
+ * The rule in the bounce loop (esc_trace_rays, esc_trace_rays_ex, esc_render_traced, esc_render_traced_ex):
+ * while the context holds an environment, at EVERY level k the line "(c, t0, id, N) = what esc_shade_rays
+ * computes" is followed by
+ *
+ *       if id is a miss: c = env(d)
+ *
+ * and everything else is unchanged: C = c at level 0, C = fl(C + fl(w * c)) afterwards, and "stop if id is
+ * a miss" still ends the path.  The environment emits nothing onto surfaces, is invisible to shadow rays
+ * and does not change which rays bounce: depth_rays, hit_rays and esc_transmit_stats are those of the same
+ * call without an environment.  Without an environment every call launches the kernels it always launched.
+ * UNCHANGED, with black where nothing is hit: esc_render_rows and everything built on the frame kernels,
+ * esc_shade_rays, esc_render_supersampled, esc_render_adaptive, the queries and ambient occlusion.
+ * Out of scope: the environment as a light source, coloured shadows, latitude / longitude maps and image
+ * loaders, filtering across faces, mip levels, a per-call switch (clear the environment instead). */
+#define ESC_ENV_MAX_RES 1024 /* the device copy holds 16 bytes per texel: 100 MB at 1024 */
+/* host_texels: 6*res*res*3 floats in HOST memory, copied (and repacked) to the device.  The environment
+ * belongs to the context and survives scene uploads; a new one replaces it; res == 0 with host_texels ==
+ * NULL removes it.  Synchronises the context's stream before and after.  res outside 0..1024, or exactly
+ * one of the two arguments being empty, is ESC_ERR_INVALID. */
+int esc_set_environment(esc_context *ctx, int32_t res, const float *host_texels);
+/* *res = R of the context's environment, 0 when none is set */
+int esc_get_environment_res(esc_context *ctx, int32_t *res);
+/* A vertical gradient as a cube, on the host, without a context or a device.  out: 6*res*res*3 floats.
+ * Texel (face, j, i) stands for D with D[axis] = +-1, D[(axis+1)%3] = ((i + 0.5)/R)*2 - 1,
+ * D[(axis+2)%3] = ((j + 0.5)/R)*2 - 1;  e = D.y / sqrt((D.x*D.x + D.y*D.y) + D.z*D.z);  the colour is
+ * horizon + (zenith - horizon)*e for e >= 0, otherwise horizon + (ground - horizon)*(-e): all in double in
+ * that operation order, then cast to float.  No libm transcendental takes part.  The result is data a
+ * caller can read, store or replace.  res outside 1..1024 or a null pointer is ESC_ERR_INVALID. */
+int esc_environment_sky(int32_t res, const float zenith[3], const float horizon[3], const float ground[3],
+                        float *out);
+/* env(d) for n directions of the caller's own (background plates; the lookup without tracing), and its PPM
+ * quantisation (main.cpp:676-682).  DEVICE pointers: d_dirs n*3 floats, d_rgb n*3 floats, d_rgb8 n*3
+ * bytes; either output may be NULL, not both.  Asynchronous on the context's stream; n == 0 launches
+ * nothing.  Needs an environment (else ESC_ERR_INVALID) but no scene. */
+int esc_environment_rays(esc_context *ctx, int64_t n, const float *d_dirs, float *d_rgb, uint8_t *d_rgb8);
+/* The same lookup on the host, for inspection and tests: the very code the kernels run (rt_environ.h),
+ * compiled for the host.  texels in the host layout above, dirs and rgb n*3 floats in host memory. */
+int esc_environment_lookup_host(int32_t res, const float *texels, int64_t n, const float *dirs, float *rgb);
 
 /* Whole frame into HOST memory, synchronous: render + D2H.  `image` = W*H*3 floats. */
 int esc_render_frame_host(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
