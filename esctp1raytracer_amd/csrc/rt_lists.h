@@ -500,6 +500,29 @@ DEVINL void tri2_listed_primary(FetchF recf, FetchE rece, const int32_t *orig, i
 // 3u of the line's direction, 3e-5 cells; rectangles are grown by 1e-3 cells.
 // Lists hold PAIR records (two neighbours of the spatial order): the reference arithmetic on
 // pair-interleaved records is what the sweeps' exact path runs (pair2_any_pk).
+//
+// One rectangle per half.  The two halves of a record are any two of the 8 spheres of a k-d leaf,
+// which seen from P can lie many cells apart: the record is appended to the cells of half 0's
+// rectangle and to those cells of half 1's rectangle that are not in half 0's -- a cell holds a
+// record at most once, and a cell that neither half's disc touches does not hold it.  (A ray needs
+// the record only where one of its spheres can be accepted: the union of the two rectangles.)
+//
+// The reach of the RECTANGLES comes from the cone of origins.  Call R0_i the reach above (W_i over B's
+// corners) and l = |c_i - P|, e = (c_i - P) / l, phi0 = asin(R0_i / l).  By the statement above, an
+// origin O in B from which sphere i can be accepted lies within delta of a point x = P + s v, s >= 0,
+// of the line shifted through P, with the angle between v and e at most phi0 (|v - e| <= 2 sin(phi0 / 2)
+// <= phi0), and x lies in B grown by delta.  For such x
+//     |x - c_i| = |s v - l e| <= |s - l| + s |v - e| <= |s - l| + s phi0,
+// convex in s, so over 0 <= s <= s_max it is at most max(l, s_max - l) + s_max phi0.  x stays in the
+// grown box: on every axis a with |e_a| > phi0 the component v_a has e_a's sign and |v_a| >= |e_a| - phi0,
+// so s <= (distance from P to the grown box's face on that side) / (|e_a| - phi0); s_max is the
+// smallest of these.  Hence every origin that matters has |O - c_i| <= W1_i := max(l, s_max - l) +
+// s_max phi0 + delta, and the first statement holds again with min(W_i, W1_i) for W_i: the lines of
+// those origins pass within R1_i = r_i (1+u) + 0x1.6p-10 min(W_i, W1_i) + delta <= R0_i of c_i after
+// the shift.  W_i is kept when P lies outside B, when no axis qualifies or when R0_i > l / 2 (the
+// cone is then too wide to say much).  Only the radius handed to sphere_pixel_extent is R1_i: `around`,
+// "wholly in front of the plane" and the cut-by-plane rule keep R0_i (they decide WHETHER a rectangle
+// is meaningful; any R in [R1_i, R0_i] is a valid radius for it).
 // ---------------------------------------------------------------------------------------
 // one wave per pair record of the group-sorted table; every listed light, every face
 __global__ void __launch_bounds__(256) k_bin_light_pairs(const RenderParams p) {
@@ -516,7 +539,10 @@ __global__ void __launch_bounds__(256) k_bin_light_pairs(const RenderParams p) {
     const double P[3] = {p.light_points[4 * LL.point[li]], p.light_points[4 * LL.point[li] + 1],
                          p.light_points[4 * LL.point[li] + 2]};
     const double delta = 0x1p-20 * (rho + fabs(P[0] - g[0]) + fabs(P[1] - g[1]) + fabs(P[2] - g[2]));
-    double c[2][3], Rh[2], cn[2];
+    bool P_in_box = true;
+    for (int k = 0; k < 3; ++k)
+      P_in_box = P_in_box && P[k] >= (double)p.scene_lo[k] && P[k] <= (double)p.scene_hi[k];
+    double c[2][3], Rh[2], Rx[2], cn[2];
     bool real[2], around[2];
     for (int h = 0; h < 2; ++h) {
       real[h] = S.r2[h] >= 0.f; // pad half: r2 = -inf
@@ -527,19 +553,36 @@ __global__ void __launch_bounds__(256) k_bin_light_pairs(const RenderParams p) {
         const double d = fmax(fabs(C[k] - (double)p.scene_lo[k]), fabs(C[k] - (double)p.scene_hi[k]));
         far2 += d * d;
       }
-      const double reach = (sqrt(fmax(0.0, (double)S.r2[h])) + 0x1.6p-10 * sqrt(far2)) * (1.0 + 0x1p-20);
-      Rh[h] = reach + delta + 0x1p-60;
+      const double rad = sqrt(fmax(0.0, (double)S.r2[h])), far = sqrt(far2);
+      Rh[h] = (rad + 0x1.6p-10 * far) * (1.0 + 0x1p-20) + delta + 0x1p-60;
       cn[h] = sqrt(dot3(c[h], c[h]));
       // P inside (or all but inside) the reach: every direction, and the "before P" argument is off
       around[h] = real[h] && !(cn[h] > Rh[h] * 1.001 + 1e-4 * rho);
+      // the rectangles' reach: origins in the cone of half-angle phi0 from P through the sphere
+      Rx[h] = Rh[h];
+      if (real[h] && P_in_box && Rh[h] <= 0.5 * cn[h]) {
+        const double phi0 = asin(Rh[h] / cn[h]) * (1.0 + 1e-9) + 1e-12;
+        double s_max = 1e300;
+        for (int k = 0; k < 3; ++k) {
+          const double e = c[h][k] / cn[h], room = fabs(e) * (1.0 - 1e-9) - phi0;
+          if (room > 0.0) {
+            const double wall = (e > 0.0 ? (double)p.scene_hi[k] - P[k] : P[k] - (double)p.scene_lo[k]) + delta;
+            s_max = fmin(s_max, wall / room);
+          }
+        }
+        if (s_max < 1e300) {
+          const double W1 = (fmax(cn[h], s_max - cn[h]) + s_max * phi0) * (1.0 + 1e-9) + delta;
+          Rx[h] = (rad + 0x1.6p-10 * fmin(far, W1)) * (1.0 + 0x1p-20) + delta + 0x1p-60;
+        }
+      }
     }
     for (int face = 0; face < 6; ++face) {
       int32_t *hdr = LL.hdr + (size_t)(li * 6 + face) * kTileHdrInts;
       int m, ia, ib;
       double sign;
       light_face_axes(face, m, ia, ib, sign);
-      bool face_global = false, have = false;
-      double ext[4] = {1e300, -1e300, 1e300, -1e300};
+      bool face_global = false;
+      int u0[2] = {0, 0}, w0[2] = {0, 0}, nx[2] = {0, 0}, nc[2] = {0, 0}; // each half's own rectangle, clipped to the face
       for (int h = 0; h < 2; ++h) {
         if (!real[h]) continue;
         if (around[h]) {
@@ -550,15 +593,17 @@ __global__ void __launch_bounds__(256) k_bin_light_pairs(const RenderParams p) {
         if (depth > Rh[h] * (1.0 + 1e-9)) { // wholly in front of the face's plane through P
           const CamD cam = light_face_frame(P, face);
           double e[4];
-          if (!sphere_pixel_extent(cam, Rr + 1, Rr + 1, c[h], Rh[h], e, nullptr, 1e-3)) {
+          if (!sphere_pixel_extent(cam, Rr + 1, Rr + 1, c[h], Rx[h], e, nullptr, 1e-3)) {
             face_global = true;
             continue;
           }
-          ext[0] = fmin(ext[0], e[0]);
-          ext[1] = fmax(ext[1], e[1]);
-          ext[2] = fmin(ext[2], e[2]);
-          ext[3] = fmax(ext[3], e[3]);
-          have = true;
+          const int u1 = min(Rr - 1, (int)floor(e[1])), w1 = min(Rr - 1, (int)floor(e[3]));
+          u0[h] = max(0, (int)floor(e[0]));
+          w0[h] = max(0, (int)floor(e[2]));
+          if (u0[h] <= u1 && w0[h] <= w1) { // (else: seen from P through other faces only)
+            nx[h] = u1 - u0[h] + 1;
+            nc[h] = nx[h] * (w1 - w0[h] + 1);
+          }
         } else {
           // cut by (or behind) the plane: relevant only if the disc reaches the face's directions,
           // all within acos(1 / sqrt 3) = 0.95532 rad of the axis
@@ -574,14 +619,14 @@ __global__ void __launch_bounds__(256) k_bin_light_pairs(const RenderParams p) {
         }
         continue;
       }
-      if (!have) continue;
-      const int u0 = max(0, (int)floor(ext[0])), u1 = min(Rr - 1, (int)floor(ext[1]));
-      const int w0 = max(0, (int)floor(ext[2])), w1 = min(Rr - 1, (int)floor(ext[3]));
-      if (u0 > u1 || w0 > w1) continue; // seen from P through other faces only
-      const int nx = u1 - u0 + 1, n = nx * (w1 - w0 + 1);
+      const int n = nc[0] + nc[1];
       const size_t cell0 = (size_t)(li * 6 + face) * cells_per_face;
       for (int k = lane; k < n; k += 64) {
-        const size_t cell = cell0 + (size_t)(w0 + k / nx) * Rr + u0 + k % nx;
+        const int h = k < nc[0] ? 0 : 1, q = k - (h ? nc[0] : 0);
+        const int u = u0[h] + q % nx[h], w = w0[h] + q / nx[h];
+        // half 1's cells inside half 0's rectangle hold the record already
+        if (h == 1 && nc[0] > 0 && u >= u0[0] && u < u0[0] + nx[0] && w >= w0[0] && w < w0[0] + nc[0] / nx[0]) continue;
+        const size_t cell = cell0 + (size_t)w * Rr + u;
         const int slot = atomicAdd(&LL.cnt[cell], 1);
         if (slot < kLightListCap) LL.ids[cell * kLightListCap + slot] = j;
       }

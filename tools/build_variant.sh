@@ -11,6 +11,7 @@ PKG=esctp1raytracer_amd
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off \
   -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -fno-slp-vectorize \
   -Iinclude -I$PKG/host -I$PKG/csrc -Wall -Wno-unused-function "$@" -shared \
-  -o $HERE/build/variants/$NAME.so $PKG/csrc/rt_kernels.hip $PKG/csrc/rt_capi.cpp $PKG/csrc/rt_multi.cpp \
-  $PKG/host/host_core.cpp $PKG/host/obj_loader.cpp $PKG/host/synth.cpp $PKG/host/accel_build.cpp -ldl
+  -o $HERE/build/variants/$NAME.so $PKG/csrc/*.hip $PKG/csrc/rt_capi.cpp $PKG/csrc/rt_multi.cpp \
+  $PKG/host/host_core.cpp $PKG/host/obj_loader.cpp $PKG/host/synth.cpp $PKG/host/accel_build.cpp \
+  $PKG/host/scene_tables.cpp -ldl
 echo built build/variants/$NAME.so
