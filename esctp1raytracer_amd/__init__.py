@@ -769,13 +769,93 @@ class Renderer:
         return (out.cpu().numpy(), u8.cpu().numpy()) if want_u8 else out.cpu().numpy()
 
     def ambient_stats(self):
-        """Counts of the last ambient_rays / render_ambient call: rays, hit_rays, samples (K * hit_rays),
+        """Counts of the last ambient_rays / render_ambient / skylight_rays / render_skylight call: rays, hit_rays, samples (K * hit_rays),
         occluded_samples, exact_rays (primary or sample rays that took the reference loop), exact_tests.
         Synchronises."""
         s = _capi.esc_ambient_stats()
         check(self._lib.esc_last_ambient_stats(self._h, C.byref(s)))
         return {k: int(getattr(s, k)) for k in ("rays", "hit_rays", "samples", "occluded_samples", "exact_rays",
                                                 "exact_tests")}
+
+    # ---- sky lighting (esc_skylight_rays / esc_render_skylight / esc_add_light) --------------------------
+    def skylight_rays(self, origins, dirs, *, sky=None, light=None, vis=None, radius=FLT_MAX, bias=1e-4, count=None,
+                      t=None, geom=None, prim=None, samples=None, sets=None, seed=0, pixel_base=0, exact=False):
+        """Sky lighting of n rays (esc_skylight_rays), asynchronous on the renderer's stream: ambient_rays'
+        samples, and what the open ones see of the environment cube.  sky (n, 3) float32 = the sum of env(w_k)
+        over the open samples / K, light (n, 3) float32 = the hit material's kd * sky; both zero for a miss.
+        Contiguous device tensors; sky or light may be None, not both; vis, count, t, geom, prim are
+        ambient_rays' outputs, each optional here.  Needs a sample table and an environment."""
+        import torch
+        n, po, pd, _ = self._query_inputs(origins, dirs, None)
+        opt = lambda name, x, dtype, shape: None if x is None else self._query_ptr(name, x, dtype, shape)  # noqa: E731
+        args = (opt("sky", sky, torch.float32, (n, 3)), opt("light", light, torch.float32, (n, 3)),
+                opt("vis", vis, torch.float32, (n,)), opt("count", count, torch.int32, (n,)),
+                opt("t", t, torch.float32, (n,)), opt("geom", geom, torch.int32, (n,)),
+                opt("prim", prim, torch.int32, (n,)))
+        o = self._ambient_options(samples, sets, radius, bias, seed, pixel_base, exact)
+        check(self._lib.esc_skylight_rays(self._h, n, po, pd, C.byref(o), *args))
+
+    def skylight(self, origins, dirs, *, radius=FLT_MAX, bias=1e-4, samples=None, sets=None, seed=0, pixel_base=0,
+                 exact=False):
+        """Synchronous sky lighting of numpy rays: {"sky", "light", "vis", "count", "t", "geom", "prim"} as
+        numpy arrays."""
+        import torch
+        to, td, _ = self._stage(origins, dirs, None)
+        n = to.shape[0]
+        dev = to.device
+        out = {"sky": torch.empty((n, 3), dtype=torch.float32, device=dev),
+               "light": torch.empty((n, 3), dtype=torch.float32, device=dev),
+               "vis": torch.empty(n, dtype=torch.float32, device=dev),
+               "count": torch.empty(n, dtype=torch.int32, device=dev),
+               "t": torch.empty(n, dtype=torch.float32, device=dev),
+               "geom": torch.empty(n, dtype=torch.int32, device=dev),
+               "prim": torch.empty(n, dtype=torch.int32, device=dev)}
+        torch.cuda.current_stream(dev).synchronize()  # the buffers were made on torch's stream
+        self.skylight_rays(to, td, radius=radius, bias=bias, samples=samples, sets=sets, seed=seed,
+                           pixel_base=pixel_base, exact=exact, **out)
+        self.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def render_skylight(self, camera, W, H, *, radius=FLT_MAX, bias=1e-4, samples=None, sets=None, seed=0,
+                        want_light=True, want_count=False, exact=False):
+        """Pixel-centre sky lighting of a frame (esc_render_skylight): skylight_rays on camera_rays(camera, W,
+        H) with pixel ids h * W + w, the rays made inside the kernel.  Returns a dict of numpy arrays: "sky"
+        (H, W, 3) and "vis" (H, W) float32, "light" (H, W, 3) when want_light, "count" (H, W) int32 when
+        want_count.  Synchronous."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = {"sky": torch.empty((H, W, 3), dtype=torch.float32, device=dev),
+               "vis": torch.empty((H, W), dtype=torch.float32, device=dev)}
+        if want_light:
+            out["light"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        if want_count:
+            out["count"] = torch.empty((H, W), dtype=torch.int32, device=dev)
+        ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None  # noqa: E731
+        o = self._ambient_options(samples, sets, radius, bias, seed, 0, exact)
+        torch.cuda.current_stream(dev).synchronize()  # the buffers were made on torch's stream
+        check(self._lib.esc_render_skylight(self._h, C.byref(camera.c), W, H, C.byref(o), ptr("sky"), ptr("light"),
+                                            ptr("vis"), ptr("count")))
+        self.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def add_light(self, image, light, *, want_u8=False):
+        """image + light per pixel and channel on the GPU (esc_add_light): two float32 numpy arrays (..., 3)
+        of the same shape.  Returns the float32 sum, and its quantised bytes when asked for.  Synchronous."""
+        import torch
+        img = np.ascontiguousarray(image, dtype=np.float32)
+        lt = np.ascontiguousarray(light, dtype=np.float32)
+        if img.shape[-1:] != (3,) or img.shape != lt.shape:
+            raise ValueError("image and light must have the same shape (..., 3)")
+        dev = torch.device("cuda", self.device)
+        ti = torch.from_numpy(img).to(dev)
+        tl = torch.from_numpy(lt).to(dev)
+        out = torch.empty_like(ti)
+        u8 = torch.empty(img.shape, dtype=torch.uint8, device=dev) if want_u8 else None
+        torch.cuda.current_stream(dev).synchronize()
+        check(self._lib.esc_add_light(self._h, img.size // 3, C.c_void_p(ti.data_ptr()), C.c_void_p(tl.data_ptr()),
+                                      C.c_void_p(out.data_ptr()), None if u8 is None else C.c_void_p(u8.data_ptr())))
+        self.synchronize()
+        return (out.cpu().numpy(), u8.cpu().numpy()) if want_u8 else out.cpu().numpy()
 
     # ---- environment cube map (esc_set_environment / esc_environment_rays) ------------------------------
     def set_environment(self, cube):

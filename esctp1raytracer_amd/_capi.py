@@ -257,6 +257,11 @@ SIGNATURES = {
                                      C.POINTER(esc_ambient_options), _P, _P]),
     "esc_modulate": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
     "esc_last_ambient_stats": (C.c_int, [_P, C.POINTER(esc_ambient_stats)]),
+    "esc_skylight_rays": (C.c_int, [_P, C.c_int64, _P, _P, C.POINTER(esc_ambient_options), _P, _P, _P, _P, _P, _P,
+                                    _P]),
+    "esc_render_skylight": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
+                                      C.POINTER(esc_ambient_options), _P, _P, _P, _P]),
+    "esc_add_light": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
     "esc_set_environment": (C.c_int, [_P, C.c_int32, _F]),
     "esc_get_environment_res": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "esc_environment_sky": (C.c_int, [C.c_int32, _F, _F, _F, _F]),

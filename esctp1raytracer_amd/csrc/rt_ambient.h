@@ -1,10 +1,12 @@
-// rt_ambient.h -- parameter blocks of ambient occlusion (esc_ambient_rays / esc_render_ambient) and of
-// the modulation of an image by a visibility (esc_modulate).  Shared by rt_ambient.hip (device) and
-// rt_capi.cpp (host).
+// rt_ambient.h -- parameter blocks of ambient occlusion (esc_ambient_rays / esc_render_ambient), of sky
+// lighting (esc_skylight_rays / esc_render_skylight: the same kernel with SKY), of the modulation of an
+// image by a visibility (esc_modulate) and of the addition of a light to an image (esc_add_light).  Shared
+// by rt_ambient.hip (device) and rt_capi.cpp (host).
 #pragma once
 #include <stdint.h>
 
 #include "rt_device.h"
+#include "rt_environ.h"
 #include "rt_query.h"
 
 namespace esc {
@@ -17,7 +19,7 @@ struct AmbientParams {
   // q.n, the per-scene sweep tables and exact_only; q.orig / q.dir are the caller's rays (the frame
   // variant makes its rays in-lane and leaves them null); q.tmax and q's outputs are unused
   QueryParams q;
-  float *vis;                 // n
+  float *vis;                 // n (SKY: or nullptr)
   int32_t *count;             // n, or nullptr (each of the four)
   float *t;
   int32_t *geom, *prim;
@@ -33,12 +35,24 @@ struct AmbientParams {
   int32_t W, H;
   float origin[3], llc[3], horizontal[3], vertical[3];
   unsigned long long *stats;  // kAmbientStats counters (zeroed per call), or nullptr: nothing is counted
+  // sky lighting (the SKY instantiations only; the others never read these)
+  EnvParams env;              // the context's cube
+  float *sky, *light;         // n x 3 each, or nullptr (not both)
+  const int32_t *sph_mat;     // material index of sphere k (already offset by n_geom)
 };
 
 struct ModulateParams {
   int64_t n;                  // pixels
   const float *rgb;           // n x 3
   const float *vis;           // n
+  float *out;                 // n x 3 (may be rgb itself), or nullptr
+  uint8_t *out8;              // n x 3, or nullptr
+};
+
+struct AddLightParams {
+  int64_t n;                  // pixels
+  const float *rgb;           // n x 3
+  const float *light;         // n x 3
   float *out;                 // n x 3 (may be rgb itself), or nullptr
   uint8_t *out8;              // n x 3, or nullptr
 };

@@ -58,7 +58,8 @@ extern "C" int esc_launch_trace_level(const esc::TraceParams *p, hipStream_t str
 extern "C" int esc_launch_adaptive_mask(const esc::AdaptiveMaskParams *p, hipStream_t stream);
 extern "C" int esc_launch_adaptive_list(const esc::AdaptiveListParams *p, hipStream_t stream);
 extern "C" int esc_launch_adaptive_refine(const esc::AdaptiveRefineParams *p, hipStream_t stream);
-extern "C" int esc_launch_ambient(const esc::AmbientParams *p, int camera, hipStream_t stream);
+extern "C" int esc_launch_ambient(const esc::AmbientParams *p, int camera, int sky, hipStream_t stream);
+extern "C" int esc_launch_add_light(const esc::AddLightParams *p, hipStream_t stream);
 extern "C" int esc_launch_environment_rays(const esc::EnvRaysParams *p, hipStream_t stream);
 extern "C" int esc_launch_modulate(const esc::ModulateParams *p, hipStream_t stream);
 extern "C" int esc_launch_assemble(const void *gathered, void *frame, size_t rank_pitch_bytes,
@@ -2555,11 +2556,12 @@ static int ambient_options_ok(const esc_context *ctx, const char *fn_, const esc
   return ESC_OK;
 }
 
-// k_ambient on n rays of an already validated call: the caller's arrays, or (cam != nullptr) the frame's
+// k_ambient on n rays of an already validated call: the caller's arrays, or (cam != nullptr) the frame's.
+// sky: the SKY instantiation, which also writes d_sky / d_light from the context's environment.
 static int ambient_launch(esc_context *ctx, const char *fn, int64_t n, const float *d_origins, const float *d_dirs,
                           const esc_camera *cam, int32_t W, int32_t H, const esc_ambient_options *o,
                           uint32_t pixel_base, float *d_vis, int32_t *d_count, float *d_t, int32_t *d_geom,
-                          int32_t *d_prim) {
+                          int32_t *d_prim, bool sky = false, float *d_sky = nullptr, float *d_light = nullptr) {
   HIP_TRY(hipSetDevice(ctx->device));
   if (!ctx->d_amstats)
     HIP_TRY(hipMalloc((void **)&ctx->d_amstats, esc::kAmbientStats * sizeof(unsigned long long)));
@@ -2588,6 +2590,13 @@ static int ambient_launch(esc_context *ctx, const char *fn, int64_t n, const flo
   p.bias = o->bias;
   p.seed = o->seed;
   p.pixel_base = pixel_base;
+  if (sky) {
+    p.env.texels = ctx->d_env;
+    p.env.res = ctx->env_res;
+    p.sky = d_sky;
+    p.light = d_light;
+    p.sph_mat = ctx->d_sph_mat;
+  }
   if (cam) {
     p.W = W;
     p.H = H;
@@ -2599,7 +2608,7 @@ static int ambient_launch(esc_context *ctx, const char *fn, int64_t n, const flo
   // ESC_AMBIENT_STATS=0: nothing is counted (the A/B of tools/ambient_time.py; the stats then read zero)
   const char *e = std::getenv("ESC_AMBIENT_STATS");
   p.stats = (e && e[0] == '0') ? nullptr : ctx->d_amstats;
-  const int rc = esc_launch_ambient(&p, cam ? 1 : 0, ctx->stream);
+  const int rc = esc_launch_ambient(&p, cam ? 1 : 0, sky ? 1 : 0, ctx->stream);
   if (rc) {
     set_error(std::string(fn) + ": k_ambient launch: " + hipGetErrorString((hipError_t)rc));
     return ESC_ERR_HIP;
@@ -2668,6 +2677,125 @@ int esc_render_ambient(esc_context *ctx, const esc_camera *cam, int32_t W, int32
   }
   return ambient_launch(ctx, fn_, (int64_t)W * H, nullptr, nullptr, cam, W, H, opts, 0u, d_vis, d_count, nullptr,
                         nullptr, nullptr);
+}
+
+// ---- sky lighting (rt_ambient.hip with SKY) -----------------------------------------
+// ambient_options_ok plus the environment the SKY kernels read
+static int skylight_options_ok(const esc_context *ctx, const char *fn, const esc_ambient_options *o) {
+  const int rc = ambient_options_ok(ctx, fn, o);
+  if (rc) return rc;
+  if (!ctx->d_env) {
+    set_error(std::string(fn) + ": no environment (esc_set_environment)");
+    return ESC_ERR_INVALID;
+  }
+  return ESC_OK;
+}
+
+int esc_skylight_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs,
+                      const esc_ambient_options *opts, float *d_sky, float *d_light, float *d_vis,
+                      int32_t *d_count, float *d_t, int32_t *d_geom, int32_t *d_prim) {
+  const char *fn_ = "esc_skylight_rays";
+  const std::string fn(fn_);
+  if (!ctx || !opts) {
+    set_error(!ctx ? fn + ": ctx is null" : fn + ": opts is null");
+    return ESC_ERR_INVALID;
+  }
+  if (n < 0) {
+    set_error(fn + ": n < 0");
+    return ESC_ERR_INVALID;
+  }
+  const int rc = skylight_options_ok(ctx, fn_, opts);
+  if (rc) return rc;
+  if (n > 0 && (!d_origins || !d_dirs || (!d_sky && !d_light))) {
+    set_error(fn + ": d_origins, d_dirs and one of d_sky, d_light are required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_origins | (uintptr_t)d_dirs | (uintptr_t)d_sky | (uintptr_t)d_light | (uintptr_t)d_vis |
+       (uintptr_t)d_count | (uintptr_t)d_t | (uintptr_t)d_geom | (uintptr_t)d_prim) & 3u) {
+    set_error(fn + ": device pointers must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error(fn + ": n exceeds one launch (2^32 - 1 workgroups of 256 rays)");
+    return ESC_ERR_INVALID;
+  }
+  return ambient_launch(ctx, fn_, n, d_origins, d_dirs, nullptr, 0, 0, opts, opts->pixel_base, d_vis, d_count, d_t,
+                        d_geom, d_prim, true, d_sky, d_light);
+}
+
+int esc_render_skylight(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
+                        const esc_ambient_options *opts, float *d_sky, float *d_light, float *d_vis,
+                        int32_t *d_count) {
+  const char *fn_ = "esc_render_skylight";
+  const std::string fn(fn_);
+  if (!ctx || !cam || !opts || (!d_sky && !d_light)) {
+    set_error(!ctx    ? fn + ": ctx is null"
+              : !opts ? fn + ": opts is null"
+              : !cam  ? fn + ": cam is null"
+                      : fn + ": one of d_sky, d_light is required");
+    return ESC_ERR_INVALID;
+  }
+  if (W < 2 || H < 2) {
+    set_error(fn + ": need W,H >= 2");
+    return ESC_ERR_INVALID;
+  }
+  if ((int64_t)W * H > 0x7fffffffLL) {
+    set_error(fn + ": W*H exceeds the reference's int pixel index (main.cpp:784)");
+    return ESC_ERR_INVALID;
+  }
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(cam->origin[k]) || !std::isfinite(cam->lower_left_corner[k]) ||
+        !std::isfinite(cam->horizontal[k]) || !std::isfinite(cam->vertical[k])) {
+      set_error(fn + ": camera is not finite");
+      return ESC_ERR_INVALID;
+    }
+  const int rc = skylight_options_ok(ctx, fn_, opts);
+  if (rc) return rc;
+  if (((uintptr_t)d_sky | (uintptr_t)d_light | (uintptr_t)d_vis | (uintptr_t)d_count) & 3u) {
+    set_error(fn + ": device pointers must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  return ambient_launch(ctx, fn_, (int64_t)W * H, nullptr, nullptr, cam, W, H, opts, 0u, d_vis, d_count, nullptr,
+                        nullptr, nullptr, true, d_sky, d_light);
+}
+
+int esc_add_light(esc_context *ctx, int64_t n, const float *d_rgb, const float *d_light, float *d_out,
+                  uint8_t *d_out8) {
+  if (!ctx) {
+    set_error("esc_add_light: ctx is null");
+    return ESC_ERR_INVALID;
+  }
+  if (n < 0) {
+    set_error("esc_add_light: n < 0");
+    return ESC_ERR_INVALID;
+  }
+  if (n > 0 && (!d_rgb || !d_light || (!d_out && !d_out8))) {
+    set_error("esc_add_light: d_rgb, d_light and one of d_out, d_out8 are required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_rgb | (uintptr_t)d_light | (uintptr_t)d_out) & 3u) {
+    set_error("esc_add_light: device pointers must be 4-byte aligned (d_out8 excepted)");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error("esc_add_light: n exceeds one launch (2^32 - 1 workgroups of 256 pixels)");
+    return ESC_ERR_INVALID;
+  }
+  if (n == 0) return ESC_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  esc::AddLightParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.n = n;
+  p.rgb = d_rgb;
+  p.light = d_light;
+  p.out = d_out;
+  p.out8 = d_out8;
+  const int rc = esc_launch_add_light(&p, ctx->stream);
+  if (rc) {
+    set_error(std::string("esc_add_light: k_add_light launch: ") + hipGetErrorString((hipError_t)rc));
+    return ESC_ERR_HIP;
+  }
+  return ESC_OK;
 }
 
 int esc_modulate(esc_context *ctx, int64_t n, const float *d_rgb, const float *d_vis, float *d_out,

@@ -53,6 +53,10 @@
 //                 esc_set_environment).  The frame is rendered through esc_render_traced_ex, at depth 0 when
 //                 --bounces is absent (one GPU, not with --ispc, --bvh, --bvh-tree or --adaptive)
 //   --sky-res N   with --sky: texels per side of the cube (1..1024, default 64)
+//   --skylight    with --sky and --ao K --ao-radius R: the sky lights the scene.  Instead of being multiplied
+//                 by the visibility, the image gains, pixel by pixel, kd times the mean of what the open ones
+//                 of the K directions see of the sky (esc_render_skylight, esc_add_light; one GPU, not with
+//                 --ispc)
 //   --help        print the options and leave
 #include <chrono>
 #include <cmath>
@@ -106,6 +110,8 @@ const char *kUsage =
     "  --ao-sets S --ao-bias B --ao-seed N   with --ao: direction sets (16), surface offset (1e-4), seed (0)\n"
     "  --sky zr,zg,zb/hr,hg,hb/gr,gg,gb   rays that leave the scene see a zenith / horizon / ground gradient\n"
     "  --sky-res N                with --sky: texels per side of the environment cube (1..1024, default 64)\n"
+    "  --skylight                 with --sky and --ao K --ao-radius R: add the sky's light on the open directions\n"
+    "                             to the image instead of multiplying it by the visibility\n"
     "  --help                     this text\n";
 
 // --ao's values: a whole number in [lo, hi], or a finite float (> 0, or >= 0), with nothing after it
@@ -161,7 +167,7 @@ int main(int argc, char *argv[]) {
   float ao_radius = 0.f, ao_bias = 1e-4f;
   unsigned long long ao_seed = 0;
   bool have_ao_radius = false, have_ao_extra = false;
-  bool sky = false, have_sky_res = false;
+  bool sky = false, have_sky_res = false, skylight = false;
   float sky_colours[9] = {0};
   int sky_res = 64;
 
@@ -277,6 +283,7 @@ int main(int argc, char *argv[]) {
       arg++;
       continue;
     }
+    if (a == "--skylight") { skylight = true; continue; }
     if (a == "--help") {
       std::cout << kUsage;
       return 0;
@@ -295,6 +302,9 @@ int main(int argc, char *argv[]) {
   if (refract && fresnel) die("--refract and --fresnel exclude each other");
   if (refract && bounces < 0) die("--refract needs --bounces");
   if (fresnel && bounces < 0) die("--fresnel needs --bounces");
+  if (skylight && (ispc || gpus != 1)) die("--skylight renders on one GPU and not with --ispc");
+  if (skylight && !sky) die("--skylight needs --sky");
+  if (skylight && (!ao || !have_ao_radius)) die("--skylight needs --ao K --ao-radius R");
   if (ao && !have_ao_radius) die("--ao needs --ao-radius");
   if (!ao && (have_ao_radius || have_ao_extra)) die("--ao-radius, --ao-sets, --ao-bias and --ao-seed need --ao");
   if (ao && (ispc || gpus != 1)) die("--ao renders on one GPU and not with --ispc");
@@ -436,19 +446,25 @@ int main(int argc, char *argv[]) {
       for (int i = 0; i < gpus; i++) std::cerr << " band " << i << " kernel ms: " << ms[i] << std::endl;
   }
   if (ao) {
-    // the frame back on the device, the pixel centres' visibility, the product in place, and home again
+    // the frame back on the device, the pixel centres' visibility (--skylight: the sky's light on them), the
+    // product (the sum) in place, and home again
     std::vector<float> table((size_t)ao_sets * ao * 3);
     check(esc_ambient_cosine_table(ao_sets, ao, ao_seed, table.data()), "ambient table");
     check(esc_set_ambient_table(ctx, ao_sets, ao, table.data()), "ambient table");
     const esc_ambient_options ao_opts = {ao, ao_sets, ao_radius, ao_bias, ao_seed, 0u, 0u};
-    float *d_image = nullptr, *d_vis = nullptr;
+    float *d_image = nullptr, *d_vis = nullptr; // d_vis: W*H visibilities, or with --skylight W*H*3 of light
     if (hipMalloc((void **)&d_image, image.size() * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&d_vis, (size_t)W * H * sizeof(float)) != hipSuccess)
+        hipMalloc((void **)&d_vis, (size_t)W * H * (skylight ? 3 : 1) * sizeof(float)) != hipSuccess)
       die("out of device memory");
     if (hipMemcpy(d_image, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
       die("copy to the device failed");
-    check(esc_render_ambient(ctx, &cam, W, H, &ao_opts, d_vis, nullptr), "ambient");
-    check(esc_modulate(ctx, (int64_t)W * H, d_image, d_vis, d_image, nullptr), "modulate");
+    if (skylight) {
+      check(esc_render_skylight(ctx, &cam, W, H, &ao_opts, nullptr, d_vis, nullptr, nullptr), "skylight");
+      check(esc_add_light(ctx, (int64_t)W * H, d_image, d_vis, d_image, nullptr), "add light");
+    } else {
+      check(esc_render_ambient(ctx, &cam, W, H, &ao_opts, d_vis, nullptr), "ambient");
+      check(esc_modulate(ctx, (int64_t)W * H, d_image, d_vis, d_image, nullptr), "modulate");
+    }
     check(esc_context_synchronize(ctx), "ambient");
     if (hipMemcpy(image.data(), d_image, image.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
       die("copy back failed");

@@ -842,7 +842,9 @@ typedef struct esc_ambient_options {
   uint32_t pixel_base; /* esc_ambient_rays: the hash's pixel of ray 0; esc_render_ambient ignores it */
   uint32_t flags;
 } esc_ambient_options;
-/* counts of the last esc_ambient_rays / esc_render_ambient call (zero before the first) */
+/* counts of the last esc_ambient_rays / esc_render_ambient / esc_skylight_rays / esc_render_skylight call
+ * (zero before the first): the sky lighting calls run the same primary and sample rays and report the same
+ * six counters */
 typedef struct esc_ambient_stats {
   uint64_t rays;
   uint64_t hit_rays;         /* rays whose closest hit found a primitive */
@@ -869,8 +871,53 @@ int esc_render_ambient(esc_context *ctx, const esc_camera *cam, int32_t W, int32
  * (main.cpp:676-682).  d_out may be d_rgb itself; d_out or d_out8 may be NULL, not both.  Asynchronous. */
 int esc_modulate(esc_context *ctx, int64_t n, const float *d_rgb, const float *d_vis, float *d_out,
                  uint8_t *d_out8);
-/* synchronises the context's stream */
+/* synchronises the context's stream; reports esc_skylight_rays / esc_render_skylight too */
 int esc_last_ambient_stats(esc_context *ctx, esc_ambient_stats *out);
+
+/* ---- sky lighting: the open ambient samples gather the environment (rt_ambient.hip, DESIGN.md section
+ * 3.19) ----
+ * The environment cube (esc_set_environment, below) as a diffuse light: the cosine-weighted mean of env(w_k)
+ * over the open samples of ambient occlusion is the diffuse irradiance estimator, image-based ambient
+ * lighting with contact shadows.  It adds no random draw and no device transcendental to what
+ * esc_ambient_rays and env(d) already consist of: + - * /, sqrt and the lookup's floor.
+ *
+ * Steps 1-7 of esc_ambient_options are unchanged: they give the hit, N, Nf, P, T, B, the set, the w_k, and
+ * open / occluded against radius, count and vis.  Then, all in fp32 with one rounding per written operation:
+ *
+ *   8. s = (+0, +0, +0).  for k = 0 .. K-1, in this order: if sample k is open:
+ *          e = env(w_k)   (env(d) of esc_set_environment on the context's cube, w_k exactly as step 6 made it)
+ *          s_c = fl(s_c + e_c)  for c = r, g, b
+ *      An occluded sample adds nothing.
+ *      sky_c = fl(s_c / float(K)).  A miss: sky = (0, 0, 0), with count = K and vis = 1 as before.
+ *   9. light_c = fl(kd_c * sky_c), kd of the hit's material (material floats 3..5; a sphere's through its
+ *      material index).  A miss: light = (0, 0, 0).
+ *
+ * A miss carries no light on purpose: traced frames already show the sky there, and frame + light must not
+ * add it twice.  The estimator divides by K, not by the open count: the samples are cosine-weighted, so sky
+ * is irradiance / pi and kd * sky is the diffuse radiance.  With an all-ones cube sky == vis in every
+ * channel, bit for bit.
+ *
+ * opts is esc_ambient_options, unchanged, with its rules.  The calls need both a sample table and an
+ * environment: a call without either is ESC_ERR_INVALID with a message naming it.  Validation, alignment,
+ * n == 0 and asynchrony follow esc_ambient_rays and esc_modulate.  vis, count, t, geom and prim are those of
+ * esc_ambient_rays with the same options, bit for bit, and esc_last_ambient_stats reports these calls too.
+ * Out of scope: the environment as a light for esc_shade_rays, frames or the bounce loop, specular or glossy
+ * reflection of the sky, importance sampling of bright texels, bounce light. */
+/* d_sky, d_light: n x 3 floats each, either may be NULL, not both; d_vis (n floats), d_count (n int32), d_t,
+ * d_geom, d_prim: each NULL or n, as esc_ambient_rays writes them */
+int esc_skylight_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs,
+                      const esc_ambient_options *opts, float *d_sky, float *d_light, float *d_vis,
+                      int32_t *d_count, float *d_t, int32_t *d_geom, int32_t *d_prim);
+/* the rays of esc_render_ambient, made inside the kernel: bit for bit esc_skylight_rays on
+ * esc_camera_rays(cam, W, H, 0, H, NULL) with pixel_base 0.  d_sky, d_light: W*H*3 floats, either may be
+ * NULL, not both; d_vis: W*H floats or NULL; d_count: W*H or NULL. */
+int esc_render_skylight(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
+                        const esc_ambient_options *opts, float *d_sky, float *d_light, float *d_vis,
+                        int32_t *d_count);
+/* d_out[3i + c] = fl(d_rgb[3i + c] + d_light[3i + c]) for n pixels, and d_out8 = its quantisation
+ * (main.cpp:676-682).  d_out may be d_rgb itself; d_out or d_out8 may be NULL, not both.  Asynchronous. */
+int esc_add_light(esc_context *ctx, int64_t n, const float *d_rgb, const float *d_light, float *d_out,
+                  uint8_t *d_out8);
 
 /* ---- environment cube map: traced rays that miss see a sky (rt_environ.h, rt_environ.hip, rt_trace.hip,
  * DESIGN.md section 3.18) ----
@@ -914,8 +961,9 @@ int esc_last_ambient_stats(esc_context *ctx, esc_ambient_stats *out);
  * call without an environment.  Without an environment every call launches the kernels it always launched.
  * UNCHANGED, with black where nothing is hit: esc_render_rows and everything built on the frame kernels,
  * esc_shade_rays, esc_render_supersampled, esc_render_adaptive, the queries and ambient occlusion.
- * Out of scope: the environment as a light source, coloured shadows, latitude / longitude maps and image
- * loaders, filtering across faces, mip levels, a per-call switch (clear the environment instead). */
+ * The environment as a diffuse light source is esc_skylight_rays (above).
+ * Out of scope: coloured shadows, latitude / longitude maps and image loaders, filtering across faces, mip
+ * levels, a per-call switch (clear the environment instead). */
 #define ESC_ENV_MAX_RES 1024 /* the device copy holds 16 bytes per texel: 100 MB at 1024 */
 /* host_texels: 6*res*res*3 floats in HOST memory, copied (and repacked) to the device.  The environment
  * belongs to the context and survives scene uploads; a new one replaces it; res == 0 with host_texels ==
