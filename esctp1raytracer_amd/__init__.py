@@ -18,7 +18,7 @@ from ._capi import (ESC_FACE_FIXED, ESC_FACE_HASH, ESC_STAGE_AUTO, ESC_STAGE_BVH
                     ESC_STAGE_SMEM, ESC_TRANSMIT_OFF, ESC_TRANSMIT_REFRACT, ESC_TRANSMIT_FRESNEL, EscError,
                     check)
 
-__all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table", "environment_sky", "environment_lookup_host",
+__all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "live_device_allocations", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table", "environment_sky", "environment_lookup_host",
            "EscError", "ESC_FACE_FIXED", "ESC_FACE_HASH", "ESC_STAGE_AUTO", "ESC_STAGE_SMEM",
            "ESC_STAGE_LDS", "ESC_STAGE_BVH", "ESC_RENDER_EXACT_ONLY", "ESC_RENDER_TIME_KERNELS", "ESC_RENDER_INDEX_ORDER", "ESC_RENDER_SHADE_QUEUE",
            "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "ESC_TRANSMIT_OFF", "ESC_TRANSMIT_REFRACT", "ESC_TRANSMIT_FRESNEL", "version"]
@@ -407,7 +407,7 @@ class Renderer:
         check(self._lib.esc_frame_record(self._h, C.byref(camera.c), W, H, strip_rows, first_strip,
                                          strip_stride, C.byref(o), self._dev_ptr(out_f32, n * 4),
                                          self._dev_ptr(out_u8, n), C.byref(h)))
-        return RecordedFrame(self._lib, h, (out_f32, out_u8))
+        return RecordedFrame(self._lib, h, (self, out_f32, out_u8))
 
     def assemble_strips(self, gathered, n_ranks, rank_pitch_bytes, W, H, frame, *, strip_rows=8,
                         bytes_per_pixel=12):
@@ -999,8 +999,13 @@ class RecordedFrame:
     """esc_frame: one frame's launches as a HIP graph on its renderer's stream"""
 
     def __init__(self, lib, handle, keep):
-        self._lib, self._h, self._keep = lib, handle, keep  # the output buffers must outlive the graph
+        # the renderer (its context, under the graph) and the output buffers must outlive the graph
+        self._lib, self._h, self._keep = lib, handle, keep
         self._launch = lib.esc_frame_launch
+
+    def valid(self):
+        """esc_frame_valid: True while launch() would be accepted (False once the renderer is closed)"""
+        return bool(self._h and self._keep[0]._h and self._lib.esc_frame_valid(self._h))
 
     def launch(self):
         rc = self._launch(self._h)
@@ -1014,6 +1019,13 @@ class RecordedFrame:
 
     def __del__(self):
         self.close()
+
+
+def live_device_allocations():
+    """esc_live_device_allocations: (buffers, bytes) the renderers of this process hold on their devices"""
+    n, b = C.c_int64(), C.c_int64()
+    check(_capi.load().esc_live_device_allocations(C.byref(n), C.byref(b)))
+    return n.value, b.value
 
 
 def strip_local_rows(H, strip_rows, first_strip, strip_stride):

@@ -191,6 +191,7 @@ SIGNATURES = {
     "esc_context_set_stream": (C.c_int, [_P, _P]),
     "esc_context_stream": (_P, [_P]),
     "esc_context_synchronize": (C.c_int, [_P]),
+    "esc_live_device_allocations": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "esc_upload_scene": (C.c_int, [_P, _P]),
     "esc_upload_flat": (C.c_int, [_P, C.c_int32, C.POINTER(ispc_triangle), C.c_int32,
                                   C.POINTER(ispc_light), C.c_int32, C.POINTER(ispc_triangle)]),
@@ -204,6 +205,7 @@ SIGNATURES = {
                                    C.c_int32, C.c_int32, C.POINTER(esc_render_options), _P, _P,
                                    C.POINTER(C.c_void_p)]),
     "esc_frame_launch": (C.c_int, [_P]),
+    "esc_frame_valid": (C.c_int, [_P]),
     "esc_frame_destroy": (None, [_P]),
     "esc_strip_local_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "esc_assemble_strips": (C.c_int, [_P, _P, C.c_int32, C.c_size_t, C.c_int32, C.c_int32,

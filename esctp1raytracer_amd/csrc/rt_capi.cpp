@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -20,6 +21,7 @@
 #include "rt_ambient.h"
 #include "rt_environ.h"
 #include "rt_device.h"
+#include "rt_devmem.h"
 #include "rt_query.h"
 #include "rt_shade_rays.h"
 #include "rt_trace.h"
@@ -96,8 +98,8 @@ struct esc_context {
   esc::DevSphPairF *d_sph2_f = nullptr;
   esc::DevSphPair *d_sph2_ord = nullptr;    // last light's sweep order (rt_device.h sph2_ord)
   esc::DevSphPairF *d_sph2_f_ord = nullptr;
-  esc::SphGroups sg{};                  // sphere groups (all pointers owned)
-  esc::TriGroups tg{};                  // triangle groups (all pointers owned)
+  esc::SphGroups sg{};                  // sphere groups
+  esc::TriGroups tg{};                  // triangle groups
   esc::DevTriF *d_tri_f = nullptr;
   esc::DevTriPairF *d_tri2_f = nullptr;
   esc::DevTriPF *d_tri_pf = nullptr;       // pre-filter forms (rt_brute.h "Triangle pre-filter")
@@ -118,9 +120,15 @@ struct esc_context {
   // state and is only valid for the epoch it was recorded in
   uint64_t epoch = 0;
   bool capturing = false; // inside esc_frame_record's stream capture: nothing may rebuild
+  // every device buffer below (and inside sg, tg, sl, tl, ll, lt, lbins) is allocated through one of
+  // these two and freed with it (rt_devmem.h).  `frame`: what a kernel launched by esc_render_strips
+  // reads or writes -- the staged scene and its tables, d_hits, the lists, the tree, the bins, d_sq,
+  // d_sq_ctl, d_counters; freeing any of it ends every recorded frame.  `call`: everything else
+  esc::DevMem frame{this, &epoch, &capturing};
+  esc::DevMem call{this};
   bool prepared = false;
   float prepared_origin[3] = {0, 0, 0};
-  int32_t *d_hits = nullptr; // k_primary -> k_shade hand-over: 3 planes (idx, t, v) of hits_cap dwords
+  int32_t *d_hits = nullptr; // k_primary -> k_shade hand-over: 3 planes (idx, t, v) of hits_cap / 3 dwords
   size_t hits_cap = 0;
   // tile lists of the primary pass (rt_device.h TileLists), valid for list_key
   esc::TileLists sl{}, tl{};
@@ -159,9 +167,8 @@ struct esc_context {
   esc::OriginBounds accel_ob{};
   esc_accel_info accel_info{};
   // queue form of the shadow pass (rt_device.h ShadeQueue): grow-only scratch
-  void *d_sq = nullptr;
-  size_t sq_pixels = 0; // pixels the scratch is sized for
-  int sq_lights = 0;
+  char *d_sq = nullptr;
+  size_t sq_bytes = 0;
   uint32_t *d_sq_ctl = nullptr;
   size_t sq_ctl_words = 0;
   int n_cu = 0;
@@ -178,12 +185,12 @@ struct esc_context {
   unsigned long long *d_sstats = nullptr;
   // esc_render_supersampled: one band's rays and colours (grow-only, at most kSsScratchBytes)
   float *d_ss = nullptr;
-  size_t ss_rays = 0;
+  size_t ss_floats = 0;
   // esc_trace_rays / esc_render_traced (rt_trace.hip): esc_trace_stats + the queue counters, and one
   // batch's queues (plus, for a frame, its rays and colours); grow-only, at most kSsScratchBytes
   unsigned long long *d_tstats = nullptr;
   float *d_tr = nullptr;
-  size_t tr_bytes = 0;
+  size_t tr_floats = 0;
   // transmission side table (tf[3], ni per material, indexed like d_mat) of esc_trace_rays_ex, and
   // whether any of its entries is transmissive: only then do the TRANSMIT kernels run
   float *d_transmit = nullptr;
@@ -209,34 +216,41 @@ struct esc_context {
   int32_t env_res = 0;
 };
 
+// ---- rt_devmem.h's backend: the only hipMalloc / hipFree of this file
+static std::atomic<int64_t> g_live_buffers{0}, g_live_bytes{0};
+
+void *esc::devmem_allocate(size_t bytes) {
+  void *p = nullptr;
+  const hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) {
+    set_error("hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
+    return nullptr;
+  }
+  g_live_buffers++;
+  g_live_bytes += (int64_t)bytes;
+  return p;
+}
+
+void esc::devmem_free(void *p, size_t bytes) {
+  (void)hipFree(p);
+  g_live_buffers--;
+  g_live_bytes -= (int64_t)bytes;
+}
+
+bool esc::devmem_wait(void *owner) {
+  const hipError_t e = hipStreamSynchronize(static_cast<const esc_context *>(owner)->stream);
+  if (e != hipSuccess) set_error(std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+  return e == hipSuccess;
+}
+
 namespace {
 
-template <typename T> int upload_vec(T *&dptr, const std::vector<T> &h, hipStream_t st) {
-  if (dptr) {
-    HIP_TRY(hipFree(dptr));
-    dptr = nullptr;
-  }
-  if (h.empty()) return ESC_OK;
-  HIP_TRY(hipMalloc((void **)&dptr, h.size() * sizeof(T)));
-  HIP_TRY(hipMemcpyAsync(dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  return ESC_OK;
-}
-
-// the tables the kernels only read are `const T *` in the parameter blocks; the context still owns them
-template <typename T> int upload_vec(const T *&dptr, const std::vector<T> &h, hipStream_t st) {
-  T *d = const_cast<T *>(dptr);
-  const int rc = upload_vec(d, h, st);
-  dptr = d;
-  return rc;
-}
-
-template <typename T> int alloc_dev(T *&dptr, size_t n) {
-  if (dptr) {
-    HIP_TRY(hipFree(dptr));
-    dptr = nullptr;
-  }
-  if (n == 0) return ESC_OK;
-  HIP_TRY(hipMalloc((void **)&dptr, n * sizeof(T)));
+// P: T, or const T for the tables the kernels only read
+template <typename P, typename T>
+int upload_vec(esc::DevMem &mem, P *&dptr, const std::vector<T> &h, hipStream_t st) {
+  const int rc = mem.alloc(dptr, h.size());
+  if (rc || h.empty()) return rc;
+  HIP_TRY(hipMemcpyAsync(const_cast<T *>(dptr), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
   return ESC_OK;
 }
 
@@ -248,45 +262,45 @@ int commit(esc_context *ctx, const Staged &s) {
   std::memcpy(ctx->scene_hi, t.scene_hi, sizeof(t.scene_hi));
   HIP_TRY(hipStreamSynchronize(ctx->stream)); // nothing in flight may still read old tables
   int rc;
-  if ((rc = upload_vec(ctx->tg.sorted, t.tg_sorted, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->tg.orig, t.tg_orig, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->tg.grp, t.tg_grp, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->tg.sorted2_pf, t.tg_sorted2_pf, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->tg.sorted2_f, t.tg_sorted2_f, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->tg.grp2_pf, t.tg_grp2_pf, ctx->stream))) return rc;
-  if ((rc = alloc_dev(ctx->tg.sorted_p, t.tg_sorted.size()))) return rc;
-  if ((rc = alloc_dev(ctx->tg.sorted_f, t.tg_sorted.size()))) return rc;
-  if ((rc = alloc_dev(ctx->tg.sorted_pf, t.tg_sorted.size()))) return rc;
-  if ((rc = alloc_dev(ctx->tg.grp_pf, t.tg_grp.size()))) return rc;
-  if ((rc = alloc_dev(ctx->tg.esc, 3 * t.tg_grp.size()))) return rc; // three chains (rt_device.h)
+  if ((rc = upload_vec(ctx->frame, ctx->tg.sorted, t.tg_sorted, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->tg.orig, t.tg_orig, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->tg.grp, t.tg_grp, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->tg.sorted2_pf, t.tg_sorted2_pf, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->tg.sorted2_f, t.tg_sorted2_f, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->tg.grp2_pf, t.tg_grp2_pf, ctx->stream))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->tg.sorted_p, t.tg_sorted.size()))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->tg.sorted_f, t.tg_sorted.size()))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->tg.sorted_pf, t.tg_sorted.size()))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->tg.grp_pf, t.tg_grp.size()))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->tg.esc, 3 * t.tg_grp.size()))) return rc; // three chains (rt_device.h)
   ctx->tg.n_grp = t.tg_n_grp;
   ctx->tg.n_sup = t.tg_n_sup;
   ctx->tg.n_hyp = t.tg_n_hyp;
-  if ((rc = upload_vec(ctx->sg.sorted2, t.sg_sorted2, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->sg.sorted2_f, t.sg_sorted2_f, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->sg.grp2_f, t.sg_grp2_f, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->sg.sorted, t.sg_sorted, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->sg.grp, t.sg_grp, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->sg.orig, t.sg_orig, ctx->stream))) return rc;
-  if ((rc = alloc_dev(ctx->sg.sorted_p, t.sg_sorted.size()))) return rc;
-  if ((rc = alloc_dev(ctx->sg.sorted_f, t.sg_sorted.size()))) return rc;
-  if ((rc = alloc_dev(ctx->sg.grp_f, t.sg_grp.size()))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->sg.sorted2, t.sg_sorted2, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->sg.sorted2_f, t.sg_sorted2_f, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->sg.grp2_f, t.sg_grp2_f, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->sg.sorted, t.sg_sorted, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->sg.grp, t.sg_grp, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->sg.orig, t.sg_orig, ctx->stream))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->sg.sorted_p, t.sg_sorted.size()))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->sg.sorted_f, t.sg_sorted.size()))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->sg.grp_f, t.sg_grp.size()))) return rc;
   ctx->sg.n_grp = t.sg_n_grp;
   ctx->sg.n_sup = t.sg_n_sup;
   ctx->sg.n_hyp = t.sg_n_hyp;
-  if ((rc = upload_vec(ctx->d_sph2_ord, t.sph2_ord, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_sph2_f_ord, t.sph2_f_ord, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_sph2_f, t.sph2_f, ctx->stream))) return rc;
-  if ((rc = alloc_dev(ctx->d_sph_f, s.sph.size()))) return rc;
-  if ((rc = upload_vec(ctx->d_tri2_f, t.tri2_f, ctx->stream))) return rc;
-  if ((rc = alloc_dev(ctx->d_tri_f, s.tri.size()))) return rc;
-  if ((rc = alloc_dev(ctx->d_tri_pf, s.tri.size()))) return rc;
-  if ((rc = upload_vec(ctx->d_tri2_pf, t.tri2_pf, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_sph2_ord, t.sph2_ord, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_sph2_f_ord, t.sph2_f_ord, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_sph2_f, t.sph2_f, ctx->stream))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->d_sph_f, s.sph.size()))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_tri2_f, t.tri2_f, ctx->stream))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->d_tri_f, s.tri.size()))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->d_tri_pf, s.tri.size()))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_tri2_pf, t.tri2_pf, ctx->stream))) return rc;
   std::memcpy(ctx->shadow_center, t.g, sizeof(t.g));
   ctx->shadow_rho_max = t.rho_max;
-  if ((rc = upload_vec(ctx->d_tri, s.tri, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_tri_n, s.tri_n, ctx->stream))) return rc;
-  if ((rc = alloc_dev(ctx->d_tri_face, s.tri.size()))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_tri, s.tri, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_tri_n, s.tri_n, ctx->stream))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->d_tri_face, s.tri.size()))) return rc;
   if (!s.tri.empty()) {
     const int e = esc_launch_face_normals(ctx->d_tri, ctx->d_tri_face, (int)s.tri.size(), ctx->stream);
     if (e) {
@@ -294,15 +308,15 @@ int commit(esc_context *ctx, const Staged &s) {
       return ESC_ERR_HIP;
     }
   }
-  if ((rc = upload_vec(ctx->d_sph, s.sph, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_sph2, t.sph2, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_sph_mat, s.sph_mat, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_mat, s.mat, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_transmit, s.transmit, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_lights, s.lights, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_light_points, s.light_points, ctx->stream))) return rc;
-  if ((rc = alloc_dev(ctx->d_tri_p, s.tri.size()))) return rc;
-  if ((rc = alloc_dev(ctx->d_sph_p, s.sph.size()))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_sph, s.sph, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_sph2, t.sph2, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_sph_mat, s.sph_mat, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_mat, s.mat, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->call, ctx->d_transmit, s.transmit, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_lights, s.lights, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_light_points, s.light_points, ctx->stream))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->d_tri_p, s.tri.size()))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->d_sph_p, s.sph.size()))) return rc;
   HIP_TRY(hipStreamSynchronize(ctx->stream)); // host vectors die with the caller's frame
   ctx->n_tri = (int)s.tri.size();
   ctx->n_sph = (int)s.sph.size();
@@ -379,19 +393,19 @@ int build_accel_device(esc_context *ctx, const float origin[3]) {
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream)); // no frame in flight may still walk the old tree
   int rc;
-  if ((rc = upload_vec(ctx->d_bvh_tri_nodes, a.tri.nodes, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_bvh_tri_blocks, a.tri_blocks, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_bvh_tri_order, a.tri.order, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_bvh_sph_nodes, a.sph.nodes, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_bvh_sph_blocks, a.sph_blocks, ctx->stream))) return rc;
-  if ((rc = upload_vec(ctx->d_bvh_sph_order, a.sph.order, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_bvh_tri_nodes, a.tri.nodes, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_bvh_tri_blocks, a.tri_blocks, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_bvh_tri_order, a.tri.order, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_bvh_sph_nodes, a.sph.nodes, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_bvh_sph_blocks, a.sph_blocks, ctx->stream))) return rc;
+  if ((rc = upload_vec(ctx->frame, ctx->d_bvh_sph_order, a.sph.order, ctx->stream))) return rc;
   static_assert(sizeof(esc::PrimBox) == sizeof(esc::PrimBoxDev), "same six floats");
   {
     std::vector<esc::PrimBoxDev> tb(a.tri_boxes.size()), sb(a.sph_boxes.size());
     if (!tb.empty()) std::memcpy(tb.data(), a.tri_boxes.data(), tb.size() * sizeof(esc::PrimBoxDev));
     if (!sb.empty()) std::memcpy(sb.data(), a.sph_boxes.data(), sb.size() * sizeof(esc::PrimBoxDev));
-    if ((rc = upload_vec(ctx->d_tri_boxes, tb, ctx->stream))) return rc;
-    if ((rc = upload_vec(ctx->d_sph_boxes, sb, ctx->stream))) return rc;
+    if ((rc = upload_vec(ctx->frame, ctx->d_tri_boxes, tb, ctx->stream))) return rc;
+    if ((rc = upload_vec(ctx->frame, ctx->d_sph_boxes, sb, ctx->stream))) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream)); // tb / sb die here
   }
   ctx->bin_tiles_x = ctx->bin_groups_y = 0; // bins hold ids of the old scene: start over
@@ -407,10 +421,10 @@ int build_accel_device(esc_context *ctx, const float origin[3]) {
       // otherwise overflow; 26 MB per light point at 128, 104 MB at 256
       g.R = n_prims <= 32768 ? 128 : 256;
       const size_t n_cells = (size_t)n_pts * 6 * g.R * g.R;
-      if ((rc = alloc_dev(g.face_hdr, (size_t)n_pts * 6 * esc::kBinHdrInts))) return rc;
-      if ((rc = alloc_dev(g.counts, 2 * n_cells))) return rc;
-      if ((rc = alloc_dev(g.tri_ids, n_cells * esc::kBinCap))) return rc;
-      if ((rc = alloc_dev(g.sph_ids, n_cells * esc::kBinCap))) return rc;
+      if ((rc = ctx->frame.alloc(g.face_hdr, (size_t)n_pts * 6 * esc::kBinHdrInts))) return rc;
+      if ((rc = ctx->frame.alloc(g.counts, 2 * n_cells))) return rc;
+      if ((rc = ctx->frame.alloc(g.tri_ids, n_cells * esc::kBinCap))) return rc;
+      if ((rc = ctx->frame.alloc(g.sph_ids, n_cells * esc::kBinCap))) return rc;
       HIP_TRY(hipMemsetAsync(g.face_hdr, 0, (size_t)n_pts * 6 * esc::kBinHdrInts * 4, ctx->stream));
       HIP_TRY(hipMemsetAsync(g.counts, 0, 2 * n_cells * 4, ctx->stream));
       HIP_TRY(hipMemsetAsync(g.tri_ids, 0, n_cells * esc::kBinCap * 4, ctx->stream));
@@ -424,8 +438,8 @@ int build_accel_device(esc_context *ctx, const float origin[3]) {
       }
     }
   }
-  if ((rc = alloc_dev(ctx->d_bvh_tri_blocks_p, a.tri_blocks.size()))) return rc;
-  if ((rc = alloc_dev(ctx->d_bvh_sph_blocks_p, a.sph_blocks.size()))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->d_bvh_tri_blocks_p, a.tri_blocks.size()))) return rc;
+  if ((rc = ctx->frame.alloc(ctx->d_bvh_sph_blocks_p, a.sph_blocks.size()))) return rc;
   ctx->accel_prepared = false;
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   const int builds = ctx->accel_info.builds;
@@ -472,12 +486,17 @@ int esc_context_create(int32_t device, esc_context **out) {
     return ESC_ERR_HIP;
   }
   ctx->own_stream = true;
-  hipError_t ce = hipMalloc((void **)&ctx->d_counters, esc::kCounterSets * 8 * sizeof(unsigned long long));
-  if (ce == hipSuccess) ce = hipMemset(ctx->d_counters, 0, esc::kCounterSets * 8 * sizeof(unsigned long long));
-  if (ce != hipSuccess) {
-    set_error(std::string("hipMalloc(counters): ") + hipGetErrorString(ce));
+  int rc = ctx->frame.alloc(ctx->d_counters, (size_t)esc::kCounterSets * 8);
+  if (rc == ESC_OK) {
+    const hipError_t ce = hipMemset(ctx->d_counters, 0, esc::kCounterSets * 8 * sizeof(unsigned long long));
+    if (ce != hipSuccess) {
+      set_error(std::string("hipMemset(counters): ") + hipGetErrorString(ce));
+      rc = ESC_ERR_HIP;
+    }
+  }
+  if (rc != ESC_OK) {
     esc_context_destroy(ctx);
-    return ESC_ERR_HIP;
+    return rc;
   }
   *out = ctx;
   return ESC_OK;
@@ -487,35 +506,10 @@ void esc_context_destroy(esc_context *ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  void *ptrs[] = {ctx->d_tri,    ctx->d_tri_p,  ctx->d_tri_n,  ctx->d_tri_face,      ctx->d_sph,      ctx->d_sph_p,
-                  ctx->d_sph2,   ctx->d_sph_f, ctx->d_sph2_f, ctx->d_sph2_ord, ctx->d_sph2_f_ord, ctx->d_tri_f, ctx->d_tri_pf, ctx->d_tri2_pf,
-                  ctx->d_tri2_f, const_cast<esc::DevSph *>(ctx->sg.sorted),
-                  const_cast<esc::DevSphGroup *>(ctx->sg.grp), const_cast<esc::DevIdx4 *>(ctx->sg.orig),
-                  ctx->sg.sorted_p, ctx->sg.sorted_f, ctx->sg.grp_f,
-                  const_cast<esc::DevSphPair *>(ctx->sg.sorted2),
-                  const_cast<esc::DevSphPairF *>(ctx->sg.sorted2_f),
-                  const_cast<esc::DevSphPairF *>(ctx->sg.grp2_f),
-                  const_cast<esc::DevTri *>(ctx->tg.sorted), const_cast<esc::DevIdx4 *>(ctx->tg.orig),
-                  const_cast<esc::DevTriGroup *>(ctx->tg.grp),
-                  const_cast<esc::DevTriPairPF *>(ctx->tg.sorted2_pf),
-                  const_cast<esc::DevTriPairF *>(ctx->tg.sorted2_f),
-                  const_cast<esc::DevTriPairPF *>(ctx->tg.grp2_pf), ctx->tg.sorted_p, ctx->tg.sorted_f,
-                  ctx->tg.sorted_pf, ctx->tg.grp_pf, ctx->tg.esc,
-                  ctx->d_sph_mat, ctx->d_mat,   ctx->d_lights,       ctx->d_light_points,
-                  ctx->d_counters, ctx->d_img,  ctx->d_u8, ctx->d_hits, ctx->d_sq, ctx->d_sq_ctl,
-                  ctx->d_bvh_tri_nodes, ctx->d_bvh_tri_blocks, ctx->d_bvh_tri_order,
-                  ctx->d_bvh_sph_nodes, ctx->d_bvh_sph_blocks, ctx->d_bvh_sph_order,
-                  ctx->d_bvh_tri_blocks_p, ctx->d_bvh_sph_blocks_p,
-                  ctx->d_tri_boxes, ctx->d_sph_boxes, ctx->d_bin_hdr, ctx->d_bin_tri_ids,
-                  ctx->d_bin_sph_ids, ctx->lbins.face_hdr, ctx->lbins.counts, ctx->lbins.tri_ids,
-                  ctx->lbins.sph_ids, ctx->d_qstats, ctx->d_sstats, ctx->d_ss, ctx->d_tstats, ctx->d_tr,
-                  ctx->d_transmit, ctx->d_astats, ctx->d_ad, ctx->d_am_table, ctx->d_amstats, ctx->d_env};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
   for (hipEvent_t ev : ctx->ev)
     if (ev) (void)hipEventDestroy(ev);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx; // its two owners free every device buffer
 }
 
 int esc_context_set_stream(esc_context *ctx, void *hip_stream) {
@@ -746,22 +740,15 @@ int render_shade_queue(esc_context *ctx, esc::RenderParams &p, int px, hipEvent_
   const size_t off_rays = 0, off_q0 = off_rays + npx * sizeof(esc::ShadowRay),
                off_q1 = off_q0 + qcap * 4,
                off_state = off_q1 + qcap * 4, total = off_state + (multi ? npx * 16 : 0);
-  if (ctx->sq_pixels < npx || (multi && ctx->sq_lights < 2)) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream)); // an earlier frame may still use the old scratch
-    if (ctx->d_sq) HIP_TRY(hipFree(ctx->d_sq));
-    ctx->d_sq = nullptr;
-    ctx->sq_pixels = 0;
-    HIP_TRY(hipMalloc(&ctx->d_sq, total));
-    ctx->sq_pixels = npx;
-    ctx->sq_lights = multi ? 2 : 1;
-  }
+  int rc;
+  if ((rc = ctx->frame.grow(ctx->d_sq, ctx->sq_bytes, total))) return rc;
   if (!ctx->n_cu) {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
     ctx->n_cu = std::max(1, prop.multiProcessorCount);
   }
-  char *base = (char *)ctx->d_sq;
-  // offsets are computed for THIS band (<= the allocation: the layout only shrinks with npx)
+  char *base = ctx->d_sq;
+  // offsets are computed for THIS band (total <= the allocation)
   p.sq.rays = (esc::ShadowRay *)(base + off_rays);
   p.sq.q[0] = (uint32_t *)(base + off_q0);
   p.sq.q[1] = (uint32_t *)(base + off_q1);
@@ -770,14 +757,7 @@ int render_shade_queue(esc_context *ctx, esc::RenderParams &p, int px, hipEvent_
   queue_segments(p.n_tri, p.n_sph, segs);
   const int n_segs = (int)segs.size() / 4;
   const size_t ctl_words = (size_t)p.n_lights * n_segs * 2;
-  if (ctx->sq_ctl_words < ctl_words) {
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->d_sq_ctl) HIP_TRY(hipFree(ctx->d_sq_ctl));
-    ctx->d_sq_ctl = nullptr;
-    ctx->sq_ctl_words = 0;
-    HIP_TRY(hipMalloc((void **)&ctx->d_sq_ctl, ctl_words * 4));
-    ctx->sq_ctl_words = ctl_words;
-  }
+  if ((rc = ctx->frame.grow(ctx->d_sq_ctl, ctx->sq_ctl_words, ctl_words))) return rc;
   p.sq.ctl = ctx->d_sq_ctl;
   HIP_TRY(hipMemsetAsync(ctx->d_sq_ctl, 0, ctl_words * 4, ctx->stream));
   int e = esc_launch_primary_only(&p, px, ctx->stream);
@@ -915,20 +895,12 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
   p.out_u8 = d_rgb_u8;
   p.counters = (opts->flags & ESC_RENDER_NO_COUNTERS) ? nullptr : ctx->d_counters;
   {
-    const size_t need = (size_t)n_local_rows * W;
-    if (ctx->hits_cap < need) {
-      // grow-only scratch; the stream is idle-synchronised so an earlier frame cannot still use it
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      if (ctx->d_hits) HIP_TRY(hipFree(ctx->d_hits));
-      ctx->d_hits = nullptr;
-      ctx->hits_cap = 0;
-      HIP_TRY(hipMalloc((void **)&ctx->d_hits, need * 3 * sizeof(int32_t)));
-      ctx->hits_cap = need;
-      ctx->epoch++;
-    }
+    const int rc = ctx->frame.grow(ctx->d_hits, ctx->hits_cap, (size_t)n_local_rows * W * 3);
+    if (rc) return rc;
+    const size_t plane = ctx->hits_cap / 3;
     p.hits.idx = ctx->d_hits;
-    p.hits.t = reinterpret_cast<float *>(ctx->d_hits + ctx->hits_cap);
-    p.hits.v = reinterpret_cast<float *>(ctx->d_hits + 2 * ctx->hits_cap);
+    p.hits.t = reinterpret_cast<float *>(ctx->d_hits + plane);
+    p.hits.v = reinterpret_cast<float *>(ctx->d_hits + 2 * plane);
   }
 
   if (!ctx->prepared || std::memcmp(ctx->prepared_origin, cam->origin, 12) != 0) {
@@ -962,25 +934,20 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
         HIP_TRY(hipStreamSynchronize(ctx->stream)); // an earlier frame may still read the old lists
         int rc;
         if (grow) {
-          void *old[] = {ctx->sl.hdr, ctx->sl.cnt, ctx->sl.ids, ctx->tl.hdr, ctx->tl.cnt, ctx->tl.ids,
-                         ctx->tl.esc};
-          for (void *q : old)
-            if (q) HIP_TRY(hipFree(q));
-          ctx->sl = esc::TileLists{};
-          ctx->tl = esc::TileLists{};
           ctx->list_tiles_cap = 0;
           ctx->lists_valid = false;
           for (esc::TileLists *L : {&ctx->sl, &ctx->tl}) {
-            if ((rc = alloc_dev(L->hdr, (size_t)esc::kTileHdrInts))) return rc;
-            if ((rc = alloc_dev(L->cnt, n_tiles))) return rc;
+            if ((rc = ctx->frame.alloc(L->hdr, (size_t)esc::kTileHdrInts))) return rc;
+            if ((rc = ctx->frame.alloc(L->cnt, n_tiles))) return rc;
+            if ((rc = ctx->frame.release(L->ids))) return rc; // sized by the old capacity: allocated again below
           }
-          if ((rc = alloc_dev(ctx->tl.esc, (size_t)esc::kTileEscCap))) return rc;
+          if ((rc = ctx->frame.alloc(ctx->tl.esc, (size_t)esc::kTileEscCap))) return rc;
           ctx->list_tiles_cap = n_tiles;
         }
         int k = 0;
         for (esc::TileLists *L : {&ctx->sl, &ctx->tl}) {
           if (need_ids[k++] && !L->ids) {
-            if ((rc = alloc_dev(L->ids, ctx->list_tiles_cap * esc::kTileListCap))) return rc;
+            if ((rc = ctx->frame.alloc(L->ids, ctx->list_tiles_cap * esc::kTileListCap))) return rc;
             // slots past a count are read in whole batches of 4: zeros are valid slots
             HIP_TRY(hipMemsetAsync(L->ids, 0, ctx->list_tiles_cap * esc::kTileListCap * 4, ctx->stream));
             ctx->lists_valid = false;
@@ -1040,12 +1007,13 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
       if (n_listed > ctx->ll_alloc_lights) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         int rc;
+        ctx->ll_alloc_lights = 0;
         for (esc::LightLists *L : {&ctx->ll, &ctx->lt}) {
-          if ((rc = alloc_dev(L->hdr, (size_t)n_listed * 6 * esc::kTileHdrInts))) return rc;
-          if ((rc = alloc_dev(L->cnt, cells))) return rc;
-          if ((rc = alloc_dev(L->ids, cells * esc::kLightListCap))) return rc;
+          if ((rc = ctx->frame.alloc(L->hdr, (size_t)n_listed * 6 * esc::kTileHdrInts))) return rc;
+          if ((rc = ctx->frame.alloc(L->cnt, cells))) return rc;
+          if ((rc = ctx->frame.alloc(L->ids, cells * esc::kLightListCap))) return rc;
         }
-        if ((rc = alloc_dev(ctx->lt.esc, (size_t)n_listed * esc::kLightEscCap))) return rc;
+        if ((rc = ctx->frame.alloc(ctx->lt.esc, (size_t)n_listed * esc::kLightEscCap))) return rc;
         ctx->ll_alloc_lights = n_listed;
         ctx->ll_valid = false;
       }
@@ -1120,9 +1088,10 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
       if (tiles_x != ctx->bin_tiles_x || groups_y != ctx->bin_groups_y) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         int rc;
-        if ((rc = alloc_dev(ctx->d_bin_hdr, esc::kBinHdrInts + 2 * n_bins))) return rc;
-        if ((rc = alloc_dev(ctx->d_bin_tri_ids, n_bins * esc::kBinCap))) return rc;
-        if ((rc = alloc_dev(ctx->d_bin_sph_ids, n_bins * esc::kBinCap))) return rc;
+        ctx->bin_tiles_x = ctx->bin_groups_y = 0;
+        if ((rc = ctx->frame.alloc(ctx->d_bin_hdr, esc::kBinHdrInts + 2 * n_bins))) return rc;
+        if ((rc = ctx->frame.alloc(ctx->d_bin_tri_ids, n_bins * esc::kBinCap))) return rc;
+        if ((rc = ctx->frame.alloc(ctx->d_bin_sph_ids, n_bins * esc::kBinCap))) return rc;
         // ids start as zeros: a slot past a bin's count must always name a valid primitive
         HIP_TRY(hipMemsetAsync(ctx->d_bin_tri_ids, 0, n_bins * esc::kBinCap * 4, ctx->stream));
         HIP_TRY(hipMemsetAsync(ctx->d_bin_sph_ids, 0, n_bins * esc::kBinCap * 4, ctx->stream));
@@ -1283,14 +1252,18 @@ int esc_frame_record(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t
     delete f;
     return ESC_ERR_HIP;
   }
+  const unsigned refused = ctx->frame.refused();
   ctx->capturing = true;
   rc = esc_render_strips(ctx, cam, W, H, strip_rows, first_strip, strip_stride, opts, d_rgb_f32,
                          d_rgb_u8);
   ctx->capturing = false;
   e = hipStreamEndCapture(ctx->stream, &f->graph);
-  if (rc == ESC_OK && (e != hipSuccess || ctx->epoch != epoch)) {
-    set_error(e != hipSuccess ? std::string("hipStreamEndCapture: ") + hipGetErrorString(e)
-                              : std::string("esc_frame_record: device state was rebuilt during the capture"));
+  // frame memory refuses to be freed or allocated inside the capture: the render then failed for that
+  if (ctx->frame.refused() != refused || (rc == ESC_OK && ctx->epoch != epoch)) {
+    set_error("esc_frame_record: device state was rebuilt during the capture");
+    rc = ESC_ERR_HIP;
+  } else if (rc == ESC_OK && e != hipSuccess) {
+    set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
     rc = ESC_ERR_HIP;
   }
   if (rc == ESC_OK) {
@@ -1310,12 +1283,14 @@ int esc_frame_record(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t
   return ESC_OK;
 }
 
+int esc_frame_valid(const esc_frame *f) { return (f && f->exec && f->ctx->epoch == f->epoch) ? 1 : 0; }
+
 int esc_frame_launch(esc_frame *f) {
   if (!f || !f->exec) {
     set_error("esc_frame_launch: bad argument");
     return ESC_ERR_INVALID;
   }
-  if (f->ctx->epoch != f->epoch) {
+  if (!esc_frame_valid(f)) {
     set_error("esc_frame_launch: the context rendered another camera, size or scene since this "
               "frame was recorded (its kernels would read rebuilt tables): record it again");
     return ESC_ERR_INVALID;
@@ -1610,7 +1585,7 @@ static int query_launch(esc_context *ctx, const char *fn, bool occ, int64_t n, c
     return ESC_ERR_INVALID;
   }
   HIP_TRY(hipSetDevice(ctx->device));
-  if (!ctx->d_qstats) HIP_TRY(hipMalloc((void **)&ctx->d_qstats, 4 * sizeof(unsigned long long)));
+  if (!ctx->d_qstats && ctx->call.alloc(ctx->d_qstats, 4)) return ESC_ERR_HIP;
   HIP_TRY(hipMemsetAsync(ctx->d_qstats, 0, 4 * sizeof(unsigned long long), ctx->stream));
   if (n == 0) return ESC_OK;
   esc::QueryParams p;
@@ -1693,7 +1668,7 @@ static int shade_options_ok(const esc_context *ctx, const char *fn, const esc_re
 }
 
 static int shade_stats_reset(esc_context *ctx) {
-  if (!ctx->d_sstats) HIP_TRY(hipMalloc((void **)&ctx->d_sstats, kShadeStats * sizeof(unsigned long long)));
+  if (!ctx->d_sstats && ctx->call.alloc(ctx->d_sstats, kShadeStats)) return ESC_ERR_HIP;
   HIP_TRY(hipMemsetAsync(ctx->d_sstats, 0, kShadeStats * sizeof(unsigned long long), ctx->stream));
   return ESC_OK;
 }
@@ -1906,13 +1881,7 @@ int esc_render_supersampled(esc_context *ctx, const esc_camera *cam, int32_t W, 
   const int64_t total = (int64_t)W * H;
   int64_t band = std::min<int64_t>(total, (int64_t)(kSsScratchBytes / (9 * sizeof(float))));
   if (band >= W) band -= band % W;
-  if (ctx->ss_rays < (size_t)band) {
-    if (ctx->d_ss) HIP_TRY(hipFree(ctx->d_ss));
-    ctx->d_ss = nullptr;
-    ctx->ss_rays = 0;
-    HIP_TRY(hipMalloc((void **)&ctx->d_ss, (size_t)band * 9 * sizeof(float)));
-    ctx->ss_rays = (size_t)band;
-  }
+  if ((rc = ctx->call.grow(ctx->d_ss, ctx->ss_floats, (size_t)band * 9))) return rc;
   float *d_o = ctx->d_ss, *d_d = ctx->d_ss + 3 * (size_t)band, *d_rgb = ctx->d_ss + 6 * (size_t)band;
   if ((rc = shade_stats_reset(ctx))) return rc;
   for (int64_t p0 = 0; p0 < total; p0 += band) {
@@ -1976,14 +1945,8 @@ int esc_render_adaptive(esc_context *ctx, const esc_camera *cam, int32_t W, int3
   if (aopts->band_rows > 0) band = std::min<int64_t>(total, (int64_t)aopts->band_rows * W);
   const size_t list_bytes = ((size_t)band * sizeof(uint32_t) + 255) & ~(size_t)255;
   const size_t need = list_bytes + (d_mask ? 0 : (size_t)total);
-  if (ctx->ad_bytes < need) {
-    if (ctx->d_ad) HIP_TRY(hipFree(ctx->d_ad));
-    ctx->d_ad = nullptr;
-    ctx->ad_bytes = 0;
-    HIP_TRY(hipMalloc((void **)&ctx->d_ad, need));
-    ctx->ad_bytes = need;
-  }
-  if (!ctx->d_astats) HIP_TRY(hipMalloc((void **)&ctx->d_astats, kAdaptiveWords * sizeof(unsigned long long)));
+  if ((rc = ctx->call.grow(ctx->d_ad, ctx->ad_bytes, need))) return rc;
+  if (!ctx->d_astats && (rc = ctx->call.alloc(ctx->d_astats, kAdaptiveWords))) return rc;
   uint32_t *d_list = (uint32_t *)ctx->d_ad;
   uint8_t *mask = d_mask ? d_mask : ctx->d_ad + list_bytes;
   uint32_t *d_count = (uint32_t *)(ctx->d_astats + esc::kAdaptiveStats);
@@ -2083,21 +2046,15 @@ static int trace_args_ok(const char *fn, int32_t max_depth, float bias) {
 }
 
 static int trace_stats_reset(esc_context *ctx) {
-  const size_t bytes = kTraceStatWords * sizeof(unsigned long long) + kTraceCounters * sizeof(uint32_t);
-  if (!ctx->d_tstats) HIP_TRY(hipMalloc((void **)&ctx->d_tstats, bytes));
+  const size_t words = kTraceStatWords + (kTraceCounters * sizeof(uint32_t) + 7) / 8; // the stats, then the counters
+  if (!ctx->d_tstats && ctx->call.alloc(ctx->d_tstats, words)) return ESC_ERR_HIP;
   HIP_TRY(hipMemsetAsync(ctx->d_tstats, 0, kTraceStatWords * sizeof(unsigned long long), ctx->stream));
   return ESC_OK;
 }
 
 // grow-only scratch of the bounce loop.  No recorded frame reads it, so no epoch is involved.
 static int trace_scratch(esc_context *ctx, size_t bytes) {
-  if (ctx->tr_bytes >= bytes) return ESC_OK;
-  if (ctx->d_tr) HIP_TRY(hipFree(ctx->d_tr));
-  ctx->d_tr = nullptr;
-  ctx->tr_bytes = 0;
-  HIP_TRY(hipMalloc((void **)&ctx->d_tr, bytes));
-  ctx->tr_bytes = bytes;
-  return ESC_OK;
+  return ctx->call.grow(ctx->d_tr, ctx->tr_floats, bytes / sizeof(float));
 }
 
 // the bounce loop on one batch of n rays: levels 0 .. max_depth, one launch each, nothing waited for.
@@ -2346,15 +2303,11 @@ int esc_set_environment(esc_context *ctx, int32_t res, const float *host_texels)
   }
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream)); // a call in flight may still read the old cube
-  if (ctx->d_env) HIP_TRY(hipFree(ctx->d_env));
-  ctx->d_env = nullptr;
   ctx->env_res = 0;
-  if (res == 0) return ESC_OK;
   std::vector<esc::EnvTexel> packed;
-  env_repack(res, host_texels, packed);
-  const size_t bytes = packed.size() * sizeof(esc::EnvTexel);
-  HIP_TRY(hipMalloc((void **)&ctx->d_env, bytes));
-  HIP_TRY(hipMemcpyAsync(ctx->d_env, packed.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (res) env_repack(res, host_texels, packed);
+  const int rc = upload_vec(ctx->call, ctx->d_env, packed, ctx->stream); // res == 0: freed, stays null
+  if (rc || res == 0) return rc;
   HIP_TRY(hipStreamSynchronize(ctx->stream)); // `packed` goes out of scope
   ctx->env_res = res;
   return ESC_OK;
@@ -2511,10 +2464,8 @@ int esc_set_ambient_table(esc_context *ctx, int32_t sets, int32_t samples, const
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream)); // a call in flight may still read the old table
   const size_t bytes = (size_t)sets * samples * 3 * sizeof(float);
-  if (ctx->d_am_table) HIP_TRY(hipFree(ctx->d_am_table));
-  ctx->d_am_table = nullptr;
   ctx->am_sets = ctx->am_samples = 0;
-  HIP_TRY(hipMalloc((void **)&ctx->d_am_table, bytes));
+  if (ctx->call.alloc(ctx->d_am_table, bytes / sizeof(float))) return ESC_ERR_HIP;
   HIP_TRY(hipMemcpyAsync(ctx->d_am_table, host_table, bytes, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream)); // host_table is the caller's again
   ctx->am_sets = sets;
@@ -2563,8 +2514,7 @@ static int ambient_launch(esc_context *ctx, const char *fn, int64_t n, const flo
                           uint32_t pixel_base, float *d_vis, int32_t *d_count, float *d_t, int32_t *d_geom,
                           int32_t *d_prim, bool sky = false, float *d_sky = nullptr, float *d_light = nullptr) {
   HIP_TRY(hipSetDevice(ctx->device));
-  if (!ctx->d_amstats)
-    HIP_TRY(hipMalloc((void **)&ctx->d_amstats, esc::kAmbientStats * sizeof(unsigned long long)));
+  if (!ctx->d_amstats && ctx->call.alloc(ctx->d_amstats, esc::kAmbientStats)) return ESC_ERR_HIP;
   HIP_TRY(hipMemsetAsync(ctx->d_amstats, 0, esc::kAmbientStats * sizeof(unsigned long long), ctx->stream));
   ctx->am_k = o->samples;
   if (n == 0) return ESC_OK;
@@ -2857,6 +2807,12 @@ int esc_last_ambient_stats(esc_context *ctx, esc_ambient_stats *out) {
   return ESC_OK;
 }
 
+int esc_live_device_allocations(int64_t *buffers, int64_t *bytes) {
+  if (buffers) *buffers = g_live_buffers.load();
+  if (bytes) *bytes = g_live_bytes.load();
+  return ESC_OK;
+}
+
 int esc_reset_counters(esc_context *ctx) {
   if (!ctx) {
     set_error("esc_reset_counters: ctx is null");
@@ -2899,21 +2855,10 @@ int esc_render_frame_host(esc_context *ctx, const esc_camera *cam, int32_t W, in
   }
   HIP_TRY(hipSetDevice(ctx->device));
   const size_t n = (size_t)W * H * 3;
-  if (image && ctx->img_cap < n) {
-    if (ctx->d_img) HIP_TRY(hipFree(ctx->d_img));
-    ctx->d_img = nullptr;
-    ctx->img_cap = 0;
-    HIP_TRY(hipMalloc((void **)&ctx->d_img, n * sizeof(float)));
-    ctx->img_cap = n;
-  }
-  if (rgb8 && ctx->u8_cap < n) {
-    if (ctx->d_u8) HIP_TRY(hipFree(ctx->d_u8));
-    ctx->d_u8 = nullptr;
-    ctx->u8_cap = 0;
-    HIP_TRY(hipMalloc((void **)&ctx->d_u8, n));
-    ctx->u8_cap = n;
-  }
-  int rc = esc_render_rows(ctx, cam, W, H, 0, H, opts, image ? ctx->d_img : nullptr,
+  int rc;
+  if (image && (rc = ctx->call.grow(ctx->d_img, ctx->img_cap, n))) return rc;
+  if (rgb8 && (rc = ctx->call.grow(ctx->d_u8, ctx->u8_cap, n))) return rc;
+  rc = esc_render_rows(ctx, cam, W, H, 0, H, opts, image ? ctx->d_img : nullptr,
                            rgb8 ? ctx->d_u8 : nullptr);
   if (rc) return rc;
   if (image)
@@ -2944,7 +2889,7 @@ int esc_render_frame_multi(const esc_scene *scene, const esc_camera *cam, int32_
   const int kStrip = 8;
   struct Band {
     esc_context *ctx = nullptr;
-    float *d_img = nullptr;
+    float *d_img = nullptr; // the band's rows, the context's call memory
     uint8_t *d_u8 = nullptr;
     hipEvent_t t0 = nullptr, t1 = nullptr;
     int rows = 0;
@@ -2955,8 +2900,6 @@ int esc_render_frame_multi(const esc_scene *scene, const esc_camera *cam, int32_
     for (auto &b : bands) {
       if (!b.ctx) continue;
       (void)hipSetDevice(b.ctx->device);
-      if (b.d_img) (void)hipFree(b.d_img);
-      if (b.d_u8) (void)hipFree(b.d_u8);
       if (b.t0) (void)hipEventDestroy(b.t0);
       if (b.t1) (void)hipEventDestroy(b.t1);
       esc_context_destroy(b.ctx);
@@ -2989,8 +2932,12 @@ int esc_render_frame_multi(const esc_scene *scene, const esc_camera *cam, int32_
     if (b.rows == 0) continue;
     const size_t n = (size_t)b.rows * W * 3;
     MULTI_TRY(hipSetDevice(b.ctx->device));
-    if (image) MULTI_TRY(hipMalloc((void **)&b.d_img, n * sizeof(float)));
-    if (rgb8) MULTI_TRY(hipMalloc((void **)&b.d_u8, n));
+    if (image) rc = b.ctx->call.alloc(b.d_img, n);
+    if (rgb8 && rc == ESC_OK) rc = b.ctx->call.alloc(b.d_u8, n);
+    if (rc != ESC_OK) {
+      cleanup();
+      return rc;
+    }
     MULTI_TRY(hipEventCreate(&b.t0));
     MULTI_TRY(hipEventCreate(&b.t1));
     MULTI_TRY(hipEventRecord(b.t0, b.ctx->stream));

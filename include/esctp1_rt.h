@@ -334,6 +334,9 @@ int esc_context_create(int32_t device, esc_context **out);
 void esc_context_destroy(esc_context *ctx);
 /* Launch on the caller's hipStream_t instead (e.g. a torch stream's handle). */
 int esc_context_set_stream(esc_context *ctx, void *hip_stream);
+/* Process-wide: how many device buffers the contexts of this library hold right now, and their bytes
+ * (either pointer may be NULL).  Destroying a context gives back everything it allocated. */
+int esc_live_device_allocations(int64_t *buffers, int64_t *bytes);
 void *esc_context_stream(esc_context *ctx);
 int esc_context_synchronize(esc_context *ctx);
 
@@ -382,13 +385,16 @@ int esc_strip_local_rows(int32_t H, int32_t strip_rows, int32_t first_strip,
  * frame replays exactly those launches -- same camera, band, options and output buffers -- and is
  * only valid while the context's per-camera / per-scene device state stands: esc_frame_launch
  * returns ESC_ERR_INVALID once the context has rendered another camera, size or scene, or had a
- * scene uploaded (record again).  Counters accumulate as for plain frames.
- * ESC_RENDER_TIME_KERNELS cannot be recorded. */
+ * scene uploaded, or has freed or reallocated any buffer a frame kernel reads or writes (record
+ * again).  Counters accumulate as for plain frames.  ESC_RENDER_TIME_KERNELS cannot be recorded. */
 typedef struct esc_frame esc_frame;
 int esc_frame_record(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t strip_rows,
                      int32_t first_strip, int32_t strip_stride, const esc_render_options *opts,
                      float *d_rgb_f32, uint8_t *d_rgb_u8, esc_frame **out);
 int esc_frame_launch(esc_frame *frame); /* asynchronous, on the context's stream */
+/* 1 when esc_frame_launch would accept the frame (the same comparison), 0 when it would refuse it or
+ * frame is NULL. */
+int esc_frame_valid(const esc_frame *frame);
 void esc_frame_destroy(esc_frame *frame);
 
 /* After a gather of N such buffers to one device (block r at d_gathered + r*rank_pitch_bytes):
