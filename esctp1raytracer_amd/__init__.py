@@ -994,6 +994,24 @@ class Renderer:
         return {"global": hdr[0], "cones": hdr[1], "off": hdr[2], "tiles_x": hdr[3], "tile_rows": hdr[4],
                 "cap": hdr[5], "global_cap": hdr[6], "counts": cnt.reshape(hdr[4], hdr[3])}
 
+    def tile_list_ids(self, which, index):
+        """esc_tile_list_ids: the entries of ONE tile / cell of the last frame's lists (`index` in the order
+        of tile_lists(which)["counts"], flattened) -> (int32 array of the stored entries, at most the list's
+        capacity; the appended count)"""
+        hdr = (C.c_int32 * 8)()
+        if check(self._lib.esc_tile_list_counts(self._h, which, hdr, None, 0)) == 0:
+            return np.zeros(0, np.int32), 0
+        cap = hdr[6] if index < 0 else hdr[5]  # global capacity / list capacity
+        ids = np.zeros(cap, np.int32)
+        n = check(self._lib.esc_tile_list_ids(self._h, which, int(index),
+                                              ids.ctypes.data_as(C.POINTER(C.c_int32)), cap))
+        return ids[:min(n, cap)].copy(), n
+
+    def tile_list_global(self, which):
+        """the global list of the tile lists (which = 0 spheres, 1 triangles): the slots every tile tests
+        -> (int32 array of the stored entries, at most the global capacity; the appended count)"""
+        return self.tile_list_ids(which, -1)
+
 
 class RecordedFrame:
     """esc_frame: one frame's launches as a HIP graph on its renderer's stream"""

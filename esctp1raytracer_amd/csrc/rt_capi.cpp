@@ -1416,9 +1416,20 @@ int esc_tile_list_counts(esc_context *ctx, int32_t which, int32_t hdr[8], int32_
 }
 
 int esc_tile_list_ids(esc_context *ctx, int32_t which, int64_t index, int32_t *ids, int32_t capacity) {
-  if (!ctx || !ids || which < 0 || which > 3 || index < 0 || capacity < 1) {
+  if (!ctx || !ids || which < 0 || which > 3 || index < -1 || (index == -1 && which >= 2) || capacity < 1) {
     set_error("esc_tile_list_ids: bad argument");
     return ESC_ERR_INVALID;
+  }
+  if (index == -1) { // the global list of the kind: hdr[0] appended, hdr[8..) the ids
+    const esc::TileLists &L = which ? ctx->tl : ctx->sl;
+    if (!ctx->lists_valid || !L.hdr) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    int32_t c = 0;
+    HIP_TRY(hipMemcpy(&c, L.hdr, 4, hipMemcpyDeviceToHost));
+    const int m = std::min(std::min(c, (int32_t)esc::kTileGlobalCap), capacity);
+    if (m > 0) HIP_TRY(hipMemcpy(ids, L.hdr + 8, (size_t)m * 4, hipMemcpyDeviceToHost));
+    return c;
   }
   const int32_t *d_ids = nullptr, *d_cnt = nullptr;
   int cap = 0;

@@ -333,6 +333,11 @@ __global__ void __launch_bounds__(256) k_bin_triangles(const RenderParams p) {
     if (lane == 0) list_global(L, k);
     return;
   }
+  // An extent at the clamp of sphere_pixel_extent (+-1e9 px): clamping moves a far corner coordinate by
+  // coordinate, which is monotone for the bounding rectangle but turns the edges of a hull -- slabs built
+  // from such extents need not hold the hull's part of the screen.  Then the rectangle alone is used.
+  const bool at_clamp = !(fabs(ext[0]) < 1e9) || !(fabs(ext[1]) < 1e9) || !(fabs(ext[2]) < 1e9) || !(fabs(ext[3]) < 1e9);
+  const bool rect_only = __builtin_amdgcn_ballot_w64(at_clamp) != 0;
   // the hull of the 12 corner rectangles along the normals of the projected triangle's three edges
   // (any direction would do for the argument; these are the ones that cut): vertex i's image is
   // taken as the mean of its four corners' centres (lanes 4 i .. 4 i + 3)
@@ -366,6 +371,10 @@ __global__ void __launch_bounds__(256) k_bin_triangles(const RenderParams p) {
   }
   int w0, w1, h0, h1;
   if (extent_rect(ext, p.W, p.H, w0, w1, h0, h1) == 2) return; // off screen
+  if (rect_only) {
+    list_rect(p, L, w0, w1, h0, h1, k, lane);
+    return;
+  }
   list_rect_hull(p, L, w0, w1, h0, h1, k, lane, HA);
 }
 

@@ -523,7 +523,10 @@ int esc_tile_list_counts(esc_context *ctx, int32_t which, int32_t hdr[8], int32_
 
 /* ... and the entries of ONE tile / cell (`index` in the order of esc_tile_list_counts): slots of
  * the group-sorted tables (which = 0, 1) or pair records (2, 3).  Returns the appended count (the
- * list holds min(count, capacity of the list) entries; at most `capacity` are copied). */
+ * list holds min(count, capacity of the list) entries; at most `capacity` are copied).
+ * index = -1 with which = 0 or 1: the GLOBAL list of that kind, the slots every tile tests (returns the
+ * appended count hdr[0]; min(count, global capacity, `capacity`) entries are copied).  The light lists
+ * (2, 3) keep one global list per face and have no such call: index = -1 is ESC_ERR_INVALID there. */
 int esc_tile_list_ids(esc_context *ctx, int32_t which, int64_t index, int32_t *ids, int32_t capacity);
 
 /* Host only, for inspection and tests: the spatial order the groups are cut from (k-d median

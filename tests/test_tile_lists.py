@@ -15,39 +15,10 @@ import zlib
 import numpy as np
 import pytest
 
-import esctp1raytracer_amd as esc
 from esctp1raytracer_amd import _capi
+from tile_list_cases import camera_struct, ref_dirs
 
 F32 = np.float32
-
-
-def ref_dirs(cam, W, H):
-    """unit directions of every pixel exactly as the reference computes them (fp32, same order)"""
-    o = np.array(cam.origin, F32)
-    llc = np.array(cam.lower_left_corner, F32)
-    hor = np.array(cam.horizontal, F32)
-    ver = np.array(cam.vertical, F32)
-    s = (np.arange(W, dtype=F32) / F32(W - 1)).astype(F32)
-    t = (np.arange(H, dtype=F32) / F32(H - 1)).astype(F32)
-    p = ((llc[None, None, :] + hor[None, None, :] * s[None, :, None]).astype(F32) +
-         (ver[None, None, :] * t[:, None, None]).astype(F32)).astype(F32)
-    p = (p - o[None, None, :]).astype(F32)
-    n2 = ((p[..., 0] * p[..., 0] + p[..., 1] * p[..., 1]).astype(F32) + p[..., 2] * p[..., 2]).astype(F32)
-    n = np.sqrt(n2).astype(F32)
-    return (p / n[..., None]).astype(F32)  # [H, W, 3]
-
-
-def camera_struct(eye, look, W, H, skew=None, vfov=60.0):
-    cam = esc.Camera.for_image(eye, look, W, H, vfov=vfov).c
-    if skew is not None:  # an image plane that is not a rectangle: the C ABI takes any four vectors
-        h = np.array(cam.horizontal, F32)
-        v = np.array(cam.vertical, F32)
-        h2 = (h + F32(skew[0]) * v).astype(F32)
-        v2 = (v + F32(skew[1]) * h).astype(F32)
-        for k in range(3):
-            cam.horizontal[k] = h2[k]
-            cam.vertical[k] = v2[k]
-    return cam
 
 
 CAMERAS = [
