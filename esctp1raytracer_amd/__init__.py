@@ -857,6 +857,106 @@ class Renderer:
         self.synchronize()
         return (out.cpu().numpy(), u8.cpu().numpy()) if want_u8 else out.cpu().numpy()
 
+    # ---- G-buffer and the edge-stopping filter (esc_gbuffer_rays / esc_render_gbuffer / esc_filter_guided) ----
+    _GBUFFER = (("normal", "float32", 3), ("position", "float32", 3), ("albedo", "float32", 3),
+                ("t", "float32", 0), ("geom", "int32", 0), ("prim", "int32", 0))
+
+    def _gbuffer_tensors(self, shape):
+        import torch
+        dev = torch.device("cuda", self.device)
+        return {k: torch.empty(tuple(shape) + ((c,) if c else ()), dtype=getattr(torch, dt), device=dev)
+                for k, dt, c in self._GBUFFER}
+
+    def gbuffer_rays(self, origins, dirs, *, normal=None, position=None, albedo=None, t=None, geom=None, prim=None,
+                     exact=False):
+        """The guides of n rays (esc_gbuffer_rays), asynchronous on the renderer's stream: normal (n, 3) = the
+        shading normal of the closest hit, not flipped towards the ray, position (n, 3) = o + d*t, albedo
+        (n, 3) = the hit material's kd, all float32 and zero for a miss, and t (n,) float32, geom, prim (n,)
+        int32 = intersect_rays' values.  Contiguous device tensors; each output may be None, not all of them.
+        exact=True: every ray through the reference loop."""
+        import torch
+        n, po, pd, _ = self._query_inputs(origins, dirs, None)
+        given = {"normal": normal, "position": position, "albedo": albedo, "t": t, "geom": geom, "prim": prim}
+        args = [None if given[k] is None else
+                self._query_ptr(k, given[k], getattr(torch, dt), (n, c) if c else (n,)) for k, dt, c in self._GBUFFER]
+        check(self._lib.esc_gbuffer_rays(self._h, n, po, pd, ESC_RENDER_EXACT_ONLY if exact else 0, *args))
+
+    def gbuffer(self, origins, dirs, *, exact=False):
+        """Synchronous G-buffer of numpy rays: {"normal", "position", "albedo", "t", "geom", "prim"} as numpy
+        arrays."""
+        import torch
+        to, td, _ = self._stage(origins, dirs, None)
+        out = self._gbuffer_tensors((to.shape[0],))
+        torch.cuda.current_stream(to.device).synchronize()  # the buffers were made on torch's stream
+        self.gbuffer_rays(to, td, exact=exact, **out)
+        self.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def render_gbuffer(self, camera, W, H, *, exact=False):
+        """The guides of a frame's pixel centres (esc_render_gbuffer): gbuffer_rays on camera_rays(camera, W, H),
+        the rays made inside the kernel.  Returns a dict of DEVICE tensors: "normal", "position", "albedo"
+        (H, W, 3) float32, "t" (H, W) float32, "geom", "prim" (H, W) int32 -- what filter_guided takes as
+        guides.  The renderer's stream is synchronised before it returns."""
+        import torch
+        out = self._gbuffer_tensors((H, W))
+        torch.cuda.current_stream(torch.device("cuda", self.device)).synchronize()
+        check(self._lib.esc_render_gbuffer(self._h, C.byref(camera.c), W, H, ESC_RENDER_EXACT_ONLY if exact else 0,
+                                           *[C.c_void_p(out[k].data_ptr()) for k, _, _ in self._GBUFFER]))
+        self.synchronize()
+        return out
+
+    def gbuffer_stats(self):
+        """Counts of the last gbuffer_rays / gbuffer / render_gbuffer call: rays, hit_rays, exact_rays,
+        exact_tests.  Synchronises."""
+        s = _capi.esc_gbuffer_stats()
+        check(self._lib.esc_last_gbuffer_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k in ("rays", "hit_rays", "exact_rays", "exact_tests")}
+
+    def filter_guided(self, image, guides, *, iterations=3, normal_cos=0.9, plane_dist, same_object=True, out=None):
+        """The edge-stopping a-trous filter (esc_filter_guided): `iterations` passes of a 5 x 5 B3-spline
+        kernel with steps 1, 2, 4, ... pixels over `image`, (H, W) or (H, W, 3) float32, a numpy array or a
+        contiguous device tensor.  A tap counts only when it is a hit of the same object (same_object) whose
+        normal has dot >= normal_cos with the pixel's and which lies within plane_dist of the pixel's tangent
+        plane; pixels without a hit are copied.  guides: the dict render_gbuffer returns ("normal", "position",
+        "geom", "prim" are read), device tensors or numpy arrays.  Returns a numpy array for a numpy image
+        (synchronous); for a device tensor a device tensor (`out`, or a new one), asynchronous on the
+        renderer's stream."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        as_numpy = not isinstance(image, torch.Tensor)
+        img = torch.from_numpy(np.array(image, dtype=np.float32, order="C")).to(dev) if as_numpy else image
+        if img.dim() not in (2, 3) or (img.dim() == 3 and img.shape[2] != 3):
+            raise ValueError("image must have shape (H, W) or (H, W, 3)")
+        H, W = int(img.shape[0]), int(img.shape[1])
+        ch = 3 if img.dim() == 3 else 1
+        pi = self._query_ptr("image", img, torch.float32, tuple(img.shape))
+        ptrs = []
+        for k, dt, c in (("normal", torch.float32, 3), ("position", torch.float32, 3), ("geom", torch.int32, 0),
+                         ("prim", torch.int32, 0)):
+            g = guides[k]
+            if not isinstance(g, torch.Tensor):
+                g = torch.from_numpy(np.array(g, dtype=np.float32 if c else np.int32, order="C")).to(dev)
+            g = g.reshape((H, W, 3) if c else (H, W))
+            ptrs.append((self._query_ptr(k, g, dt, (H, W, 3) if c else (H, W)), g))
+        if out is None:
+            out = torch.empty_like(img)
+        po = self._query_ptr("out", out, torch.float32, tuple(img.shape))
+        o = _capi.esc_filter_options(int(iterations), float(normal_cos), float(plane_dist), int(bool(same_object)))
+        torch.cuda.current_stream(dev).synchronize()  # copies and buffers were made on torch's stream
+        check(self._lib.esc_filter_guided(self._h, W, H, ch, pi, *[p for p, _ in ptrs], C.byref(o), po))
+        if as_numpy:
+            self.synchronize()
+            return out.cpu().numpy()
+        self._filter_keep = (img, [g for _, g in ptrs])  # alive until the next call: the launch is asynchronous
+        return out
+
+    def filter_stats(self):
+        """Counts of the last filter_guided call: pixels, hit_pixels, taps_tested and taps_accepted (both summed
+        over the iterations).  Synchronises."""
+        s = _capi.esc_filter_stats()
+        check(self._lib.esc_last_filter_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k in ("pixels", "hit_pixels", "taps_tested", "taps_accepted")}
+
     # ---- environment cube map (esc_set_environment / esc_environment_rays) ------------------------------
     def set_environment(self, cube):
         """esc_set_environment: cube is a (6, R, R, 3) float32 array, faces +x, -x, +y, -y, +z, -z

@@ -138,6 +138,21 @@ class esc_ambient_stats(C.Structure):  # 48 bytes
                 ("occluded_samples", C.c_uint64), ("exact_rays", C.c_uint64), ("exact_tests", C.c_uint64)]
 
 
+class esc_gbuffer_stats(C.Structure):  # 32 bytes
+    _fields_ = [("rays", C.c_uint64), ("hit_rays", C.c_uint64), ("exact_rays", C.c_uint64),
+                ("exact_tests", C.c_uint64)]
+
+
+class esc_filter_options(C.Structure):  # 24 bytes
+    _fields_ = [("iterations", C.c_int32), ("normal_cos", C.c_float), ("plane_dist", C.c_float),
+                ("same_object", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class esc_filter_stats(C.Structure):  # 32 bytes
+    _fields_ = [("pixels", C.c_uint64), ("hit_pixels", C.c_uint64), ("taps_tested", C.c_uint64),
+                ("taps_accepted", C.c_uint64)]
+
+
 class esc_bvh_node(C.Structure):  # 64 bytes
     _fields_ = [("lo0", C.c_float * 3), ("hi0", C.c_float * 3), ("lo1", C.c_float * 3),
                 ("hi1", C.c_float * 3), ("child", C.c_int32 * 2), ("minkey", C.c_uint32 * 2)]
@@ -264,6 +279,13 @@ SIGNATURES = {
     "esc_render_skylight": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
                                       C.POINTER(esc_ambient_options), _P, _P, _P, _P]),
     "esc_add_light": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P]),
+    "esc_gbuffer_rays": (C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "esc_render_gbuffer": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32, C.c_uint32, _P, _P, _P, _P,
+                                     _P, _P]),
+    "esc_last_gbuffer_stats": (C.c_int, [_P, C.POINTER(esc_gbuffer_stats)]),
+    "esc_filter_guided": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                    C.POINTER(esc_filter_options), _P]),
+    "esc_last_filter_stats": (C.c_int, [_P, C.POINTER(esc_filter_stats)]),
     "esc_set_environment": (C.c_int, [_P, C.c_int32, _F]),
     "esc_get_environment_res": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "esc_environment_sky": (C.c_int, [C.c_int32, _F, _F, _F, _F]),

@@ -22,6 +22,8 @@
 #include "rt_environ.h"
 #include "rt_device.h"
 #include "rt_devmem.h"
+#include "rt_filter.h"
+#include "rt_gbuffer.h"
 #include "rt_query.h"
 #include "rt_shade_rays.h"
 #include "rt_trace.h"
@@ -64,6 +66,9 @@ extern "C" int esc_launch_ambient(const esc::AmbientParams *p, int camera, int s
 extern "C" int esc_launch_add_light(const esc::AddLightParams *p, hipStream_t stream);
 extern "C" int esc_launch_environment_rays(const esc::EnvRaysParams *p, hipStream_t stream);
 extern "C" int esc_launch_modulate(const esc::ModulateParams *p, hipStream_t stream);
+extern "C" int esc_launch_gbuffer(const esc::GBufferParams *p, int camera, hipStream_t stream);
+extern "C" int esc_launch_filter_pack(const esc::FilterPackParams *p, hipStream_t stream);
+extern "C" int esc_launch_filter_atrous(const esc::FilterParams *p, int channels, int64_t tiles, hipStream_t stream);
 extern "C" int esc_launch_assemble(const void *gathered, void *frame, size_t rank_pitch_bytes,
                                    int n_ranks, int H, int strip_rows, size_t row_bytes,
                                    hipStream_t stream);
@@ -214,6 +219,16 @@ struct esc_context {
   // context's, not the scene's.  nullptr: traced rays that miss stay black
   esc::EnvTexel *d_env = nullptr;
   int32_t env_res = 0;
+  // the G-buffer (rt_gbuffer.hip): esc_gbuffer_stats' device counters, allocated by the first call
+  unsigned long long *d_gbstats = nullptr;
+  // esc_filter_guided (rt_filter.hip): esc_filter_stats' device counters and the last call's W*H, and the
+  // scratch (grow-only): one 32-byte guide record per pixel, and one image for the iterations to alternate with
+  unsigned long long *d_flstats = nullptr;
+  uint64_t fl_pixels = 0;
+  esc::FilterGuide *d_fl_guide = nullptr;
+  size_t fl_guide_cap = 0;
+  float *d_fl_img = nullptr;
+  size_t fl_img_cap = 0;
 };
 
 // ---- rt_devmem.h's backend: the only hipMalloc / hipFree of this file
@@ -2815,6 +2830,274 @@ int esc_last_ambient_stats(esc_context *ctx, esc_ambient_stats *out) {
   out->occluded_samples = h[2];
   out->exact_rays = h[3];
   out->exact_tests = h[4];
+  return ESC_OK;
+}
+
+// ---- the G-buffer of rays and frames (rt_gbuffer.hip) -------------------------------
+// k_gbuffer on n rays of an already validated call: the caller's arrays, or (cam != nullptr) the frame's
+static int gbuffer_launch(esc_context *ctx, const char *fn, int64_t n, const float *d_origins, const float *d_dirs,
+                          const esc_camera *cam, int32_t W, int32_t H, uint32_t flags, float *d_normal,
+                          float *d_position, float *d_albedo, float *d_t, int32_t *d_geom, int32_t *d_prim) {
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!ctx->d_gbstats && ctx->call.alloc(ctx->d_gbstats, esc::kGBufferStats)) return ESC_ERR_HIP;
+  HIP_TRY(hipMemsetAsync(ctx->d_gbstats, 0, esc::kGBufferStats * sizeof(unsigned long long), ctx->stream));
+  if (n == 0) return ESC_OK;
+  esc::GBufferParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.q.n = n;
+  p.q.orig = d_origins;
+  p.q.dir = d_dirs;
+  query_tables(ctx, p.q);
+  p.q.exact_only = (flags & ESC_RENDER_EXACT_ONLY) ? 1 : 0;
+  p.normal = d_normal;
+  p.position = d_position;
+  p.albedo = d_albedo;
+  p.t = d_t;
+  p.geom = d_geom;
+  p.prim = d_prim;
+  p.tri_n = ctx->d_tri_n;
+  p.mat = ctx->d_mat;
+  p.sph_mat = ctx->d_sph_mat;
+  if (cam) {
+    p.W = W;
+    p.H = H;
+    std::memcpy(p.origin, cam->origin, 12);
+    std::memcpy(p.llc, cam->lower_left_corner, 12);
+    std::memcpy(p.horizontal, cam->horizontal, 12);
+    std::memcpy(p.vertical, cam->vertical, 12);
+  }
+  p.stats = ctx->d_gbstats;
+  const int rc = esc_launch_gbuffer(&p, cam ? 1 : 0, ctx->stream);
+  if (rc) {
+    set_error(std::string(fn) + ": k_gbuffer launch: " + hipGetErrorString((hipError_t)rc));
+    return ESC_ERR_HIP;
+  }
+  return ESC_OK;
+}
+
+// the checks esc_gbuffer_rays and esc_render_gbuffer share, after ctx is known not to be null
+static int gbuffer_args_ok(const esc_context *ctx, const std::string &fn, int64_t n, uint32_t flags,
+                           const void *d_normal, const void *d_position, const void *d_albedo, const void *d_t,
+                           const void *d_geom, const void *d_prim) {
+  if (!ctx->have_scene) {
+    set_error(fn + ": no scene uploaded (esc_upload_scene / esc_upload_flat)");
+    return ESC_ERR_INVALID;
+  }
+  if (flags & ~(uint32_t)ESC_RENDER_EXACT_ONLY) {
+    set_error(fn + ": flags takes 0 or ESC_RENDER_EXACT_ONLY only");
+    return ESC_ERR_INVALID;
+  }
+  if (n > 0 && !d_normal && !d_position && !d_albedo && !d_t && !d_geom && !d_prim) {
+    set_error(fn + ": one of d_normal, d_position, d_albedo, d_t, d_geom, d_prim is required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_normal | (uintptr_t)d_position | (uintptr_t)d_albedo | (uintptr_t)d_t | (uintptr_t)d_geom |
+       (uintptr_t)d_prim) & 3u) {
+    set_error(fn + ": device pointers must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  return ESC_OK;
+}
+
+int esc_gbuffer_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs, uint32_t flags,
+                     float *d_normal, float *d_position, float *d_albedo, float *d_t, int32_t *d_geom,
+                     int32_t *d_prim) {
+  const char *fn_ = "esc_gbuffer_rays";
+  const std::string fn(fn_);
+  if (!ctx) {
+    set_error(fn + ": ctx is null");
+    return ESC_ERR_INVALID;
+  }
+  if (n < 0) {
+    set_error(fn + ": n < 0");
+    return ESC_ERR_INVALID;
+  }
+  const int rc = gbuffer_args_ok(ctx, fn, n, flags, d_normal, d_position, d_albedo, d_t, d_geom, d_prim);
+  if (rc) return rc;
+  if (n > 0 && (!d_origins || !d_dirs)) {
+    set_error(fn + ": d_origins and d_dirs are required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_origins | (uintptr_t)d_dirs) & 3u) {
+    set_error(fn + ": device pointers must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error(fn + ": n exceeds one launch (2^32 - 1 workgroups of 256 rays)");
+    return ESC_ERR_INVALID;
+  }
+  return gbuffer_launch(ctx, fn_, n, d_origins, d_dirs, nullptr, 0, 0, flags, d_normal, d_position, d_albedo, d_t,
+                        d_geom, d_prim);
+}
+
+int esc_render_gbuffer(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, uint32_t flags,
+                       float *d_normal, float *d_position, float *d_albedo, float *d_t, int32_t *d_geom,
+                       int32_t *d_prim) {
+  const char *fn_ = "esc_render_gbuffer";
+  const std::string fn(fn_);
+  if (!ctx || !cam) {
+    set_error(!ctx ? fn + ": ctx is null" : fn + ": cam is null");
+    return ESC_ERR_INVALID;
+  }
+  if (W < 2 || H < 2) {
+    set_error(fn + ": need W,H >= 2");
+    return ESC_ERR_INVALID;
+  }
+  if ((int64_t)W * H > 0x7fffffffLL) {
+    set_error(fn + ": W*H exceeds the reference's int pixel index (main.cpp:784)");
+    return ESC_ERR_INVALID;
+  }
+  for (int k = 0; k < 3; k++)
+    if (!std::isfinite(cam->origin[k]) || !std::isfinite(cam->lower_left_corner[k]) ||
+        !std::isfinite(cam->horizontal[k]) || !std::isfinite(cam->vertical[k])) {
+      set_error(fn + ": camera is not finite");
+      return ESC_ERR_INVALID;
+    }
+  const int rc =
+      gbuffer_args_ok(ctx, fn, (int64_t)W * H, flags, d_normal, d_position, d_albedo, d_t, d_geom, d_prim);
+  if (rc) return rc;
+  return gbuffer_launch(ctx, fn_, (int64_t)W * H, nullptr, nullptr, cam, W, H, flags, d_normal, d_position,
+                        d_albedo, d_t, d_geom, d_prim);
+}
+
+int esc_last_gbuffer_stats(esc_context *ctx, esc_gbuffer_stats *out) {
+  if (!ctx || !out) {
+    set_error(!ctx ? "esc_last_gbuffer_stats: ctx is null" : "esc_last_gbuffer_stats: out is null");
+    return ESC_ERR_INVALID;
+  }
+  unsigned long long h[esc::kGBufferStats] = {0, 0, 0, 0};
+  if (ctx->d_gbstats) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_gbstats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  out->rays = h[0];
+  out->hit_rays = h[1];
+  out->exact_rays = h[2];
+  out->exact_tests = h[3];
+  return ESC_OK;
+}
+
+// ---- the edge-stopping a-trous filter (rt_filter.hip) -------------------------------
+int esc_filter_guided(esc_context *ctx, int32_t W, int32_t H, int32_t channels, const float *d_in,
+                      const float *d_normal, const float *d_position, const int32_t *d_geom, const int32_t *d_prim,
+                      const esc_filter_options *opts, float *d_out) {
+  const std::string fn("esc_filter_guided");
+  if (!ctx || !opts) {
+    set_error(!ctx ? fn + ": ctx is null" : fn + ": opts is null");
+    return ESC_ERR_INVALID;
+  }
+  if (W < 1 || H < 1) {
+    set_error(fn + ": need W,H >= 1");
+    return ESC_ERR_INVALID;
+  }
+  if (channels != 1 && channels != 3) {
+    set_error(fn + ": channels must be 1 or 3");
+    return ESC_ERR_INVALID;
+  }
+  if (opts->iterations < 1 || opts->iterations > esc::kFilterMaxIter) {
+    set_error(fn + ": iterations must be in 1 .. 8");
+    return ESC_ERR_INVALID;
+  }
+  if (std::isnan(opts->normal_cos)) {
+    set_error(fn + ": normal_cos must not be NaN");
+    return ESC_ERR_INVALID;
+  }
+  if (!(opts->plane_dist >= 0.f)) {
+    set_error(fn + ": plane_dist must be >= 0 and not NaN (FLT_MAX or inf: off)");
+    return ESC_ERR_INVALID;
+  }
+  if (opts->same_object != 0 && opts->same_object != 1) {
+    set_error(fn + ": same_object must be 0 or 1");
+    return ESC_ERR_INVALID;
+  }
+  if (opts->reserved[0] || opts->reserved[1]) {
+    set_error(fn + ": reserved must be 0");
+    return ESC_ERR_INVALID;
+  }
+  if (!d_in || !d_normal || !d_position || !d_geom || !d_prim || !d_out) {
+    set_error(fn + ": d_in, d_normal, d_position, d_geom, d_prim and d_out are required");
+    return ESC_ERR_INVALID;
+  }
+  if (d_in == d_out) {
+    set_error(fn + ": d_out must not be d_in");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_in | (uintptr_t)d_normal | (uintptr_t)d_position | (uintptr_t)d_geom | (uintptr_t)d_prim |
+       (uintptr_t)d_out) & 3u) {
+    set_error(fn + ": device pointers must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  const int64_t n = (int64_t)W * H;
+  const int64_t tiles_x = ((int64_t)W + esc::kFilterTileW - 1) / esc::kFilterTileW;
+  const int64_t tiles = tiles_x * (((int64_t)H + esc::kFilterTileH - 1) / esc::kFilterTileH);
+  if (tiles > (int64_t)0x7fffffff || n > (int64_t)0xffffffffu * 256) {
+    set_error(fn + ": W*H exceeds one launch (2^31 - 1 tiles of 64 x 4 pixels)");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!ctx->d_flstats && ctx->call.alloc(ctx->d_flstats, esc::kFilterStats)) return ESC_ERR_HIP;
+  const int L = opts->iterations;
+  if (ctx->call.grow(ctx->d_fl_guide, ctx->fl_guide_cap, (size_t)n)) return ESC_ERR_HIP;
+  if (L > 1 && ctx->call.grow(ctx->d_fl_img, ctx->fl_img_cap, (size_t)n * (size_t)channels)) return ESC_ERR_HIP;
+  HIP_TRY(hipMemsetAsync(ctx->d_flstats, 0, esc::kFilterStats * sizeof(unsigned long long), ctx->stream));
+  ctx->fl_pixels = (uint64_t)n;
+  esc::FilterPackParams k;
+  std::memset(&k, 0, sizeof(k));
+  k.n = n;
+  k.normal = d_normal;
+  k.position = d_position;
+  k.geom = d_geom;
+  k.prim = d_prim;
+  k.guide = ctx->d_fl_guide;
+  k.stats = ctx->d_flstats;
+  int rc = esc_launch_filter_pack(&k, ctx->stream);
+  if (rc) {
+    set_error(fn + ": k_filter_pack launch: " + hipGetErrorString((hipError_t)rc));
+    return ESC_ERR_HIP;
+  }
+  esc::FilterParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.W = W;
+  p.H = H;
+  p.same_object = opts->same_object;
+  p.normal_cos = opts->normal_cos;
+  p.plane_dist = opts->plane_dist;
+  p.tiles_x = tiles_x;
+  p.guide = ctx->d_fl_guide;
+  p.stats = ctx->d_flstats;
+  // the last iteration lands in d_out: iteration i writes d_out when L - 1 - i is even, else the scratch
+  const float *src = d_in;
+  for (int i = 0; i < L; i++) {
+    float *dst = ((L - 1 - i) & 1) ? ctx->d_fl_img : d_out;
+    p.step = 1 << i;
+    p.in = src;
+    p.out = dst;
+    rc = esc_launch_filter_atrous(&p, channels, tiles, ctx->stream);
+    if (rc) {
+      set_error(fn + ": k_filter_atrous launch: " + hipGetErrorString((hipError_t)rc));
+      return ESC_ERR_HIP;
+    }
+    src = dst;
+  }
+  return ESC_OK;
+}
+
+int esc_last_filter_stats(esc_context *ctx, esc_filter_stats *out) {
+  if (!ctx || !out) {
+    set_error(!ctx ? "esc_last_filter_stats: ctx is null" : "esc_last_filter_stats: out is null");
+    return ESC_ERR_INVALID;
+  }
+  unsigned long long h[esc::kFilterStats] = {0, 0, 0};
+  if (ctx->d_flstats) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(h, ctx->d_flstats, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  out->pixels = ctx->d_flstats ? ctx->fl_pixels : 0;
+  out->hit_pixels = h[0];
+  out->taps_tested = h[1];
+  out->taps_accepted = h[2];
   return ESC_OK;
 }
 

@@ -48,6 +48,13 @@
 //   --ao-sets S   with --ao: S (1..64, default 16) sets of K cosine-weighted directions, one drawn per pixel
 //   --ao-bias B   with --ao: the sample rays start B (finite, >= 0; default 1e-4) off the surface
 //   --ao-seed N   with --ao: seed of the direction table and of the per-pixel draw (default 0)
+//   --denoise L   with --ao: the visibility (--skylight: the light) goes through L (1..8) iterations of the
+//                 edge-stopping a-trous filter before it meets the image, guided by the frame's normals, hit
+//                 positions and object ids (esc_render_gbuffer, esc_filter_guided)
+//   --denoise-normal C  with --denoise: a neighbour counts when its normal has dot >= C with the pixel's
+//                 (default 0.9)
+//   --denoise-plane X   with --denoise: ... and it lies within X (>= 0) of the pixel's tangent plane (default
+//                 --ao-radius / 4)
 //   --sky Z/H/G   environment: a vertical gradient (zenith, horizon, ground colours, each r,g,b; finite) that
 //                 the rays which leave the scene see, primary rays and bounces alike (esc_environment_sky,
 //                 esc_set_environment).  The frame is rendered through esc_render_traced_ex, at depth 0 when
@@ -108,6 +115,8 @@ const char *kUsage =
     "  --fresnel                  with --bounces: Schlick's term picks reflection or refraction per sample\n"
     "  --ao K --ao-radius R       multiply the image by the visibility of K hemisphere directions within R\n"
     "  --ao-sets S --ao-bias B --ao-seed N   with --ao: direction sets (16), surface offset (1e-4), seed (0)\n"
+    "  --denoise L                with --ao: L (1..8) passes of the edge-stopping filter over vis / light\n"
+    "  --denoise-normal C --denoise-plane X   with --denoise: normal (0.9) and plane (--ao-radius / 4) stops\n"
     "  --sky zr,zg,zb/hr,hg,hb/gr,gg,gb   rays that leave the scene see a zenith / horizon / ground gradient\n"
     "  --sky-res N                with --sky: texels per side of the environment cube (1..1024, default 64)\n"
     "  --skylight                 with --sky and --ao K --ao-radius R: add the sky's light on the open directions\n"
@@ -168,6 +177,9 @@ int main(int argc, char *argv[]) {
   unsigned long long ao_seed = 0;
   bool have_ao_radius = false, have_ao_extra = false;
   bool sky = false, have_sky_res = false, skylight = false;
+  int denoise = 0;
+  float denoise_normal = 0.9f, denoise_plane = 0.f;
+  bool have_denoise_extra = false, have_denoise_plane = false;
   float sky_colours[9] = {0};
   int sky_res = 64;
 
@@ -276,6 +288,23 @@ int main(int argc, char *argv[]) {
       arg++;
       continue;
     }
+    if (a == "--denoise") { denoise = (int)parse_whole("--denoise", next, 1, 8); arg++; continue; }
+    if (a == "--denoise-normal") {
+      if (!next) die("--denoise-normal needs a value");
+      char *end = nullptr;
+      denoise_normal = std::strtof(next, &end);
+      if (end == next || *end != '\0' || !std::isfinite(denoise_normal))
+        die(std::string("--denoise-normal must be a finite number, got ") + next);
+      have_denoise_extra = true;
+      arg++;
+      continue;
+    }
+    if (a == "--denoise-plane") {
+      denoise_plane = parse_finite("--denoise-plane", next, true);
+      have_denoise_extra = have_denoise_plane = true;
+      arg++;
+      continue;
+    }
     if (a == "--sky") { parse_sky(next, sky_colours); sky = true; arg++; continue; }
     if (a == "--sky-res") {
       sky_res = (int)parse_whole("--sky-res", next, 1, ESC_ENV_MAX_RES);
@@ -308,6 +337,8 @@ int main(int argc, char *argv[]) {
   if (ao && !have_ao_radius) die("--ao needs --ao-radius");
   if (!ao && (have_ao_radius || have_ao_extra)) die("--ao-radius, --ao-sets, --ao-bias and --ao-seed need --ao");
   if (ao && (ispc || gpus != 1)) die("--ao renders on one GPU and not with --ispc");
+  if (denoise && !ao) die("--denoise needs --ao");
+  if (!denoise && have_denoise_extra) die("--denoise-normal and --denoise-plane need --denoise");
   if (have_sky_res && !sky) die("--sky-res needs --sky");
   if (sky && (ispc || flat || gpus != 1)) die("--sky renders on one GPU and not with --ispc, --bvh or --bvh-tree");
   if (sky && have_adaptive) die("--sky is seen by traced frames: not with --adaptive");
@@ -458,14 +489,30 @@ int main(int argc, char *argv[]) {
       die("out of device memory");
     if (hipMemcpy(d_image, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
       die("copy to the device failed");
-    if (skylight) {
-      check(esc_render_skylight(ctx, &cam, W, H, &ao_opts, nullptr, d_vis, nullptr, nullptr), "skylight");
-      check(esc_add_light(ctx, (int64_t)W * H, d_image, d_vis, d_image, nullptr), "add light");
-    } else {
-      check(esc_render_ambient(ctx, &cam, W, H, &ao_opts, d_vis, nullptr), "ambient");
-      check(esc_modulate(ctx, (int64_t)W * H, d_image, d_vis, d_image, nullptr), "modulate");
+    if (skylight) check(esc_render_skylight(ctx, &cam, W, H, &ao_opts, nullptr, d_vis, nullptr, nullptr), "skylight");
+    else check(esc_render_ambient(ctx, &cam, W, H, &ao_opts, d_vis, nullptr), "ambient");
+    float *d_guides = nullptr, *d_filtered = nullptr;
+    const float *d_use = d_vis;
+    if (denoise) {
+      // --denoise: the frame's guides (normal, position | geom, prim), then the filter on vis / light
+      const size_t n = (size_t)W * H, ch = skylight ? 3 : 1;
+      if (hipMalloc((void **)&d_guides, n * 8 * sizeof(float)) != hipSuccess ||
+          hipMalloc((void **)&d_filtered, n * ch * sizeof(float)) != hipSuccess)
+        die("out of device memory");
+      float *d_normal = d_guides, *d_position = d_guides + 3 * n;
+      int32_t *d_geom = reinterpret_cast<int32_t *>(d_guides + 6 * n), *d_prim = d_geom + n;
+      check(esc_render_gbuffer(ctx, &cam, W, H, 0u, d_normal, d_position, nullptr, nullptr, d_geom, d_prim), "gbuffer");
+      const esc_filter_options f_opts = {denoise, denoise_normal, have_denoise_plane ? denoise_plane : ao_radius / 4.f,
+                                         1, {0, 0}};
+      check(esc_filter_guided(ctx, W, H, (int32_t)ch, d_vis, d_normal, d_position, d_geom, d_prim, &f_opts, d_filtered),
+            "denoise");
+      d_use = d_filtered;
     }
+    if (skylight) check(esc_add_light(ctx, (int64_t)W * H, d_image, d_use, d_image, nullptr), "add light");
+    else check(esc_modulate(ctx, (int64_t)W * H, d_image, d_use, d_image, nullptr), "modulate");
     check(esc_context_synchronize(ctx), "ambient");
+    (void)hipFree(d_guides);
+    (void)hipFree(d_filtered);
     if (hipMemcpy(image.data(), d_image, image.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
       die("copy back failed");
     (void)hipFree(d_image);

@@ -928,6 +928,109 @@ int esc_render_skylight(esc_context *ctx, const esc_camera *cam, int32_t W, int3
 int esc_add_light(esc_context *ctx, int64_t n, const float *d_rgb, const float *d_light, float *d_out,
                   uint8_t *d_out8);
 
+/* ---- G-buffer of rays and frames, and the edge-stopping a-trous filter it guides (rt_gbuffer.hip,
+ * rt_filter.hip) ----
+ * Ambient occlusion and sky lighting estimate every pixel from K <= 64 samples drawn by a hash, so vis, sky
+ * and light are banded or noisy.  The filter averages such an image over neighbouring pixels of the same
+ * surface; which neighbours those are is decided by per-pixel guides: the shading normal, the hit position
+ * and the surface's id.  The G-buffer calls hand the guides out.
+ *
+ * The G-buffer, per ray (o, d).  All arithmetic is fp32 with one rounding per operation, in vec.h's order,
+ * exactly as steps 1-2 of esc_ambient_options:
+ *
+ *   (t, id)  = the closest hit esc_intersect_rays finds with bound FLT_MAX; t, geom, prim are its outputs
+ *   normal   = the normal esc_shade_rays computes (main.cpp:723-738 incl. quirk S1, u = 0; a sphere:
+ *              normalize((o + d*t) - C)).  It is NOT flipped towards the ray.
+ *   position = fl(o + fl(d*t))
+ *   albedo   = kd of the hit's material (material floats 3..5; a sphere's through its material index)
+ *   a miss:    normal = position = albedo = (+0, +0, +0), t = FLT_MAX, geom = prim = -1
+ *
+ * Each of the six outputs may be NULL, not all of them (when n > 0).  flags: 0 or ESC_RENDER_EXACT_ONLY (every
+ * ray through the index-order loop).  Pointer, alignment, n == 0 and asynchrony rules are esc_ambient_rays'; only
+ * per-scene tables are read, and no sample table or environment is needed.  t, geom and prim are
+ * byte-identical to what esc_ambient_rays and esc_intersect_rays write for the same rays. */
+typedef struct esc_gbuffer_stats {
+  uint64_t rays;
+  uint64_t hit_rays;    /* rays whose closest hit found a primitive */
+  uint64_t exact_rays;  /* rays that took the index-order reference loop */
+  uint64_t exact_tests; /* (ray, primitive) pairs that ran the reference arithmetic */
+} esc_gbuffer_stats;
+/* d_normal, d_position, d_albedo: n x 3 floats each; d_t: n floats; d_geom, d_prim: n int32 */
+int esc_gbuffer_rays(esc_context *ctx, int64_t n, const float *d_origins, const float *d_dirs, uint32_t flags,
+                     float *d_normal, float *d_position, float *d_albedo, float *d_t, int32_t *d_geom,
+                     int32_t *d_prim);
+/* ray i = h*W + w is ray i of esc_camera_rays(cam, W, H, 0, H, NULL), made inside the kernel: bit for bit
+ * esc_gbuffer_rays on those rays.  The outputs hold W*H rays.  W, H and cam follow esc_render_ambient. */
+int esc_render_gbuffer(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, uint32_t flags,
+                       float *d_normal, float *d_position, float *d_albedo, float *d_t, int32_t *d_geom,
+                       int32_t *d_prim);
+/* counts of the last esc_gbuffer_rays / esc_render_gbuffer call (zero before the first); synchronises the
+ * context's stream */
+int esc_last_gbuffer_stats(esc_context *ctx, esc_gbuffer_stats *out);
+
+/* The filter: L iterations of a 5 x 5 a-trous (with holes) B3-spline kernel whose taps are accepted or
+ * rejected by COMPARES on the guides and weighted by the kernel's dyadic constants alone.  It consists of
+ * + - * / and compares: the usual exp() edge weights are deliberately not used, because no transcendental
+ * may run on the device, and so the result is comparable bit for bit.
+ *
+ * Images are interleaved (channels = 1 or 3 floats per pixel) and pixel (w, h) is at h*W + w, in the image
+ * and in the four guide arrays (d_normal, d_position: W*H x 3 floats; d_geom, d_prim: W*H int32, as
+ * esc_render_gbuffer writes them).  With
+ *
+ *   hit(p)    = geom[p] >= 0 || prim[p] >= 0
+ *   K1        = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *   k(dx, dy) = K1[dx+2] * K1[dy+2]                                      (exact in fp32)
+ *
+ * I_0 = in, and for i = 0 .. L-1 with s = 1 << i, I_{i+1} at pixel p = (w, h) is, all in fp32 with one
+ * rounding per written operation:
+ *
+ *   if !hit(p):  I_{i+1}[p] = I_i[p]                                     (copied, bit for bit)
+ *   else:  acc_c = +0 for every channel;  ws = +0
+ *     for dy = -2 .. 2 (ascending), inside it dx = -2 .. 2 (ascending):
+ *        q = (w + dx*s, h + dy*s);   skip unless 0 <= q.w < W and 0 <= q.h < H     (no clamping, no mirroring)
+ *        if (dx, dy) != (0, 0):                                                    -> taps_tested += 1
+ *           skip unless hit(q)
+ *           skip if same_object and !(geom[q] == geom[p] && (geom[p] >= 0 || prim[q] == prim[p]))
+ *           skip unless dot(N_p, N_q) >= normal_cos                  (vec.h dot: sum = 0; sum += a_i*b_i)
+ *           skip unless fabsf(dot(P_q - P_p, N_p)) <= plane_dist     (the difference per component first)
+ *                                                                                  -> taps_accepted += 1
+ *        acc_c = fl(acc_c + fl(k(dx,dy) * I_i[q]_c));   ws = fl(ws + k(dx,dy))
+ *     I_{i+1}[p]_c = fl(acc_c / ws)
+ *   out = I_L
+ *
+ * The centre tap is never tested, so ws >= 9/64, and a pixel with NaN guides still gets fl(fl(k0*v)/k0).
+ * A comparison with a NaN guide is false, so that tap is skipped.  A NaN or infinite image value spreads to
+ * whatever accepts it, as written.  "same object" is the same geometry for triangles and the same sphere
+ * for spheres.  The stats are summed over the L iterations; pixels = W*H and hit_pixels are counted once.
+ *
+ * d_out must not be d_in (ESC_ERR_INVALID), so no iteration reads what it writes: the iterations alternate
+ * between d_out and one context-owned scratch image so that the last one lands in d_out (L odd:
+ * in -> out -> S -> out ...; L even: in -> S -> out ...).  Scratch, owned by the context, grow-only and
+ * freed with it: 32 bytes per pixel for the packed guides (N.xyz, geom, P.xyz, prim), and for L >= 2 one
+ * image of 4 * channels bytes per pixel.  Growing it waits for the context's stream; otherwise the call is
+ * asynchronous on the stream with no host synchronisation.  It needs no scene.
+ * ESC_ERR_INVALID: iterations outside 1..8, channels other than 1 or 3, a NaN threshold, a negative
+ * plane_dist, same_object other than 0 / 1, a non-zero reserved, W or H < 1, a null or misaligned pointer.
+ * Out of scope: temporal accumulation, variance-guided weights, any smooth weight, albedo demodulation. */
+typedef struct esc_filter_options {
+  int32_t iterations;  /* L, 1..8: iteration i uses step 2^i pixels */
+  float normal_cos;    /* a tap needs dot(N_p, N_q) >= normal_cos; not NaN */
+  float plane_dist;    /* ... and |dot(P_q - P_p, N_p)| <= plane_dist; >= 0, not NaN; FLT_MAX or inf: off */
+  int32_t same_object; /* 0 / 1: ... and the same geometry (triangles) or the same sphere */
+  int32_t reserved[2]; /* 0 */
+} esc_filter_options;
+typedef struct esc_filter_stats {
+  uint64_t pixels;        /* W*H */
+  uint64_t hit_pixels;    /* pixels with hit(p): the others are copied */
+  uint64_t taps_tested;   /* non-centre taps inside the image of hit pixels, over all iterations */
+  uint64_t taps_accepted; /* ... that passed every stop */
+} esc_filter_stats;
+int esc_filter_guided(esc_context *ctx, int32_t W, int32_t H, int32_t channels, const float *d_in,
+                      const float *d_normal, const float *d_position, const int32_t *d_geom, const int32_t *d_prim,
+                      const esc_filter_options *opts, float *d_out);
+/* counts of the last esc_filter_guided call (zero before the first); synchronises the context's stream */
+int esc_last_filter_stats(esc_context *ctx, esc_filter_stats *out);
+
 /* ---- environment cube map: traced rays that miss see a sky (rt_environ.h, rt_environ.hip, rt_trace.hip,
  * DESIGN.md section 3.18) ----
  * An extension beyond the reference, whose framebuffer is black where nothing is hit.  The texels are DATA
