@@ -1112,6 +1112,33 @@ class Renderer:
         -> (int32 array of the stored entries, at most the global capacity; the appended count)"""
         return self.tile_list_ids(which, -1)
 
+    def light_lists(self, which):
+        """esc_light_list_read: the light lists of the last frame (which = 2 sphere pair records, 3 triangle
+        pair records) as numpy arrays, or None when the frame used none -> dict: "n_listed", "R", "cap",
+        "global_cap", "point" (n_listed,) rows of the light_points table, "face_counts" (n_listed, 6),
+        "face_ids" (n_listed, 6, global_cap), "counts" (n_listed, 6, R, R) indexed [light, face, cw, cu] and
+        "ids" (n_listed, 6, R, R, cap); an id array holds a list's stored ids first, then -1"""
+        info = (C.c_int32 * 8)()
+        i32 = C.POINTER(C.c_int32)
+        n = check(self._lib.esc_light_list_read(self._h, which, info, None, None, 0, 0, None))
+        if n == 0:
+            return None
+        n_listed, R, cap, gcap = info[0], info[1], info[2], info[3]
+        per_light = 6 * R * R
+        face_counts = np.zeros((n_listed, 6), np.int32)
+        face_ids = np.zeros((n_listed, 6, gcap), np.int32)
+        ids = np.zeros((n_listed, 6, R, R, cap), np.int32)
+        for li in range(n_listed):  # one copy per light
+            check(self._lib.esc_light_list_read(self._h, which, info, face_counts.ctypes.data_as(i32),
+                                                face_ids.ctypes.data_as(i32), li * per_light, per_light,
+                                                ids[li].ctypes.data_as(i32)))
+        counts = np.zeros(n, np.int32)
+        hdr = (C.c_int32 * 8)()
+        check(self._lib.esc_tile_list_counts(self._h, which, hdr, counts.ctypes.data_as(i32), n))
+        return {"n_listed": n_listed, "R": R, "cap": cap, "global_cap": gcap,
+                "point": np.array(list(info[4:4 + n_listed]), np.int32), "face_counts": face_counts,
+                "face_ids": face_ids, "counts": counts.reshape(n_listed, 6, R, R), "ids": ids}
+
 
 class RecordedFrame:
     """esc_frame: one frame's launches as a HIP graph on its renderer's stream"""

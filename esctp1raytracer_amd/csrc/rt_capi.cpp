@@ -1058,6 +1058,8 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
         }
         ctx->ll.n_listed = ctx->lt.n_listed = n_listed;
         ctx->ll.R = ctx->lt.R = Rr;
+        std::memcpy(ctx->ll.point, p.ll.point, sizeof(p.ll.point)); // (for esc_light_list_read)
+        std::memcpy(ctx->lt.point, p.lt.point, sizeof(p.lt.point));
         ctx->ll_face_mode = opts->face_mode;
         ctx->ll_fixed_face = opts->fixed_face;
         ctx->ll_valid = true;
@@ -1471,6 +1473,50 @@ int esc_tile_list_ids(esc_context *ctx, int32_t which, int64_t index, int32_t *i
   const int m = std::min(std::min(c, cap), capacity);
   if (m > 0) HIP_TRY(hipMemcpy(ids, d_ids + index * cap, (size_t)m * 4, hipMemcpyDeviceToHost));
   return c;
+}
+
+int esc_light_list_read(esc_context *ctx, int32_t which, int32_t info[8], int32_t *face_counts,
+                        int32_t *face_ids, int64_t first_cell, int64_t n_cells, int32_t *cell_ids) {
+  if (!ctx || !info || (which != 2 && which != 3) || first_cell < 0 || n_cells < 0) {
+    set_error("esc_light_list_read: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  const esc::LightLists &L = which == 2 ? ctx->ll : ctx->lt;
+  if (!ctx->ll_valid || !L.hdr || !L.cnt || !L.ids || (which == 2 ? ctx->sg.n_grp : ctx->tg.n_grp) == 0) return 0;
+  const int n_faces = L.n_listed * 6;
+  const int64_t total = (int64_t)n_faces * L.R * L.R;
+  if (first_cell > total || n_cells > total - first_cell) {
+    set_error("esc_light_list_read: cells out of range");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const int32_t out[8] = {L.n_listed, L.R, esc::kLightListCap, esc::kTileGlobalCap,
+                          L.point[0], L.point[1], L.point[2], L.point[3]};
+  std::memcpy(info, out, sizeof(out));
+  if (face_counts || face_ids) {
+    std::vector<int32_t> hdr((size_t)n_faces * esc::kTileHdrInts);
+    HIP_TRY(hipMemcpy(hdr.data(), L.hdr, hdr.size() * 4, hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_faces; f++) {
+      const int32_t *h = &hdr[(size_t)f * esc::kTileHdrInts];
+      if (face_counts) face_counts[f] = h[0];
+      if (face_ids) {
+        const int m = std::max(0, std::min(h[0], (int32_t)esc::kTileGlobalCap));
+        for (int k = 0; k < esc::kTileGlobalCap; k++)
+          face_ids[(size_t)f * esc::kTileGlobalCap + k] = k < m ? h[8 + k] : -1;
+      }
+    }
+  }
+  if (cell_ids && n_cells > 0) {
+    std::vector<int32_t> cnt((size_t)n_cells);
+    HIP_TRY(hipMemcpy(cnt.data(), L.cnt + first_cell, (size_t)n_cells * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cell_ids, L.ids + first_cell * esc::kLightListCap,
+                      (size_t)n_cells * esc::kLightListCap * 4, hipMemcpyDeviceToHost));
+    for (int64_t c = 0; c < n_cells; c++) // slots past a cell's count hold stale (valid) records: not stored ids
+      for (int k = std::max(0, std::min(cnt[(size_t)c], (int32_t)esc::kLightListCap)); k < esc::kLightListCap; k++)
+        cell_ids[(size_t)c * esc::kLightListCap + k] = -1;
+  }
+  return (int)total;
 }
 
 int esc_tile_rect(const esc_camera *cam, int32_t W, int32_t H, const float centre[3], double radius,

@@ -798,6 +798,8 @@ DEVINL bool anyhit_sph_light_lists(const LightLists &LL, int cell, FetchE rece, 
 //    within H_t + |P - O| beta_t of the plane.  Per triangle and light that is one comparison; the
 //    few triangles that pass leave an entry (n_t, beta_t) and k_bin_light_tri_escape appends them to
 //    every cell that holds a direction v with |v . n_t| <= beta_t |v| (v . n_t is affine over a cell).
+//    A cell that holds the pair record already -- inside its (S_t) rectangle, or from the entry of the pair's
+//    other triangle -- is left as it is: a cell holds a record at most once, as in the sphere lists.
 // ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_bin_light_tri_pairs(const RenderParams p) {
   const int j = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
@@ -1011,6 +1013,13 @@ __global__ void __launch_bounds__(256) k_bin_light_tri_escape(const RenderParams
     const double hi = fA + fmax(u0 * fU, u1 * fU) + fmax(w0 * fW, w1 * fW);
     const double wd = (double)X.kp * vmax + 1e-12;
     if ((lo <= wd && hi >= -wd) || !(fA == fA)) {
+      // a cell holds a record at most once: the pair may be here already, through its (S_t) rectangle or
+      // through the entry of its other triangle (this thread alone appends to the cell in this kernel, and
+      // k_bin_light_tri_pairs has finished; a cell over its cap takes the sweep whatever it holds)
+      const int have = min(LL.cnt[cell], kLightListCap);
+      bool held = false;
+      for (int q = 0; q < have; ++q) held = held || LL.ids[(size_t)cell * kLightListCap + q] == X.pair;
+      if (held) continue;
       const int slot = atomicAdd(&LL.cnt[cell], 1);
       if (slot < kLightListCap) LL.ids[(size_t)cell * kLightListCap + slot] = X.pair;
     }

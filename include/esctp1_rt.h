@@ -529,6 +529,22 @@ int esc_tile_list_counts(esc_context *ctx, int32_t which, int32_t hdr[8], int32_
  * (2, 3) keep one global list per face and have no such call: index = -1 is ESC_ERR_INVALID there. */
 int esc_tile_list_ids(esc_context *ctx, int32_t which, int64_t index, int32_t *ids, int32_t capacity);
 
+/* ... and the light lists (which = 2 sphere pair records, 3 triangle pair records) as a whole, for
+ * inspection and tests; read-only.  info receives {lights with lists, cells per face side R, list
+ * capacity, global capacity, point[0..3]}: point[li] is the row of the light_points table the lists of
+ * light li were built for.  Cells are numbered ((light * 6 + face) * R + cw) * R + cu, the order of
+ * esc_tile_list_counts.  Each of the three outputs may be NULL:
+ *   face_counts [lights * 6]                    the appended count of every (light, face) list;
+ *   face_ids    [lights * 6][global capacity]   its stored ids, min(count, global capacity) of them, then -1;
+ *   cell_ids    [n_cells][list capacity]        the stored ids of cells first_cell .. first_cell + n_cells - 1,
+ *                                               min(count, list capacity) of each, then -1 -- one copy
+ *                                               for the whole range.
+ * Returns the number of cells of all lists, 0 when the context holds no light lists of that kind (nothing
+ * is written then), or a negative error (a range that leaves the lists: ESC_ERR_INVALID).  Synchronises
+ * the context's stream. */
+int esc_light_list_read(esc_context *ctx, int32_t which, int32_t info[8], int32_t *face_counts,
+                        int32_t *face_ids, int64_t first_cell, int64_t n_cells, int32_t *cell_ids);
+
 /* Host only, for inspection and tests: the spatial order the groups are cut from (k-d median
  * splits over the points; csrc/rt_device.h SphGroups / TriGroups).  xyz holds 3 floats per point;
  * order receives a permutation of 0 .. count-1 whose consecutive runs of `run`, `big` and `huge`

@@ -315,8 +315,9 @@ float orc_pow(float x, float Ns) {
 /* ---------------------------------------------------------------- scan_row */
 
 /* main.cpp:698-791, triangle branch (num_triangles == 0) */
+/* rec (may be NULL): the row's part of orc_shadow_ray_record's output, W * n_lights * 8 floats */
 static void scan_row(const orc_scene *s, const orc_camera *cam, int32_t W, int32_t H, int32_t h,
-                     const orc_options *o, float *row_out /* W*3 */, orc_counters *cnt) {
+                     const orc_options *o, float *row_out /* W*3 */, orc_counters *cnt, float *rec) {
   const float eps = FLT_EPSILON;
   const int quirk_s1 = (o->quirks & ORC_QUIRK_S1) != 0;
   const int quirk_s3 = (o->quirks & ORC_QUIRK_S3) != 0;
@@ -404,7 +405,17 @@ static void scan_row(const orc_scene *s, const orc_camera *cam, int32_t W, int32
 
       if (o->shadows) {
         cnt->shadow_rays++;
-        if (occlusion(s, hitp, L, &t, &cnt->anyhit_tests)) continue; /* :772 */
+        float *r = rec ? &rec[((int64_t)w * s->n_lights + li) * 8] : NULL;
+        if (r) {
+          memcpy(r, hitp, sizeof(hitp));
+          memcpy(r + 3, L, sizeof(L));
+          r[6] = t;
+          r[7] = 1.f;
+        }
+        if (occlusion(s, hitp, L, &t, &cnt->anyhit_tests)) { /* :772 */
+          if (r) r[7] = 2.f;
+          continue;
+        }
       }
       float d = orc_dot(N, L); /* :775 */
       if (d <= 0) continue;    /* :777 */
@@ -448,7 +459,7 @@ static void *worker(void *p) {
   for (int32_t i = a->tid; i < a->n_rows; i += a->n_threads) {
     const int32_t h = a->rows[i];
     float *out = a->image + (int64_t)(a->packed ? i : h) * a->W * 3;
-    scan_row(a->scene, a->cam, a->W, a->H, h, a->opts, out, &a->cnt);
+    scan_row(a->scene, a->cam, a->W, a->H, h, a->opts, out, &a->cnt, NULL);
   }
   return NULL;
 }
@@ -504,6 +515,18 @@ void orc_render_row_list(const orc_scene *scene, const orc_camera *cam, int32_t 
                          const int32_t *rows, int32_t n_rows, const orc_options *opts,
                          float *packed_rows, orc_counters *counters, int32_t n_threads) {
   run_rows(scene, cam, W, H, rows, n_rows, 1, opts, packed_rows, counters, n_threads);
+}
+
+/* Test aid: the shadow rays scan_row traces, as it traces them.  record: H * W * n_lights * 8 floats,
+ * zero-filled by the caller; for pixel h * W + w and light li {hitp xyz, L xyz, the ray's initial t,
+ * 1 traced and not occluded / 2 occluded}; a pixel that hits nothing keeps its zeros.  One thread. */
+void orc_shadow_ray_record(const orc_scene *scene, const orc_camera *cam, int32_t W, int32_t H,
+                           const orc_options *opts, float *record) {
+  float *row = (float *)malloc(sizeof(float) * 3 * (size_t)(W > 0 ? W : 1));
+  orc_counters cnt = {0, 0, 0, 0};
+  for (int32_t h = H - 1; h >= 0; h--)
+    scan_row(scene, cam, W, H, h, opts, row, &cnt, record + (int64_t)h * W * scene->n_lights * 8);
+  free(row);
 }
 
 /* ------------------------------------------------------------ PPM (S12) */

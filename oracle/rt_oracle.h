@@ -170,6 +170,13 @@ void orc_render_row_list(const orc_scene *scene, const orc_camera *cam, int32_t 
                          const int32_t *rows, int32_t n_rows, const orc_options *opts,
                          float *packed_rows, orc_counters *counters, int32_t n_threads);
 
+/* Test aid: the shadow rays scan_row traces, as it traces them (with opts->shadows).  record: H * W *
+ * n_lights * 8 floats, zero-filled by the caller; for pixel h * W + w and light li it receives {hitp xyz,
+ * L xyz, the ray's initial t = len - eps, 1 = traced and not occluded / 2 = occluded}.  A pixel that hits
+ * nothing keeps its zeros.  Single-threaded. */
+void orc_shadow_ray_record(const orc_scene *scene, const orc_camera *cam, int32_t W, int32_t H,
+                           const orc_options *opts, float *record);
+
 /* main.cpp:676-682: clamp >1, int(c*255); out = W*H*3 bytes in the SAME (h*W+w) order */
 void orc_quantise(const float *image, int64_t n_values, uint8_t *out);
 

@@ -327,6 +327,47 @@ def _case_far():
     return make_case(centre=(1300.0, -1000.0, 1150.0), n_tri=64, n_sph=64)
 
 
+def _case_two_shells():
+    """the lattice twice along the SAME 64 directions, at radius 1.4 to 1.6 and at twice that, both kinds,
+    each occluder with the angular size and turn of its twin: seen from P an outer occluder fills the
+    directions its inner twin fills, so nearly every ray that needs it is occluded by the twin as well and
+    no frame shows whether the outer one was listed"""
+    c = make_case()
+    dirs, rad = lattice(64)
+    rad = 1.4 + 0.1 * (rad - 1.0)
+    is_tri = np.arange(64) % 2 == 0
+    c["tris"] = np.concatenate([small_triangles(c["p"], dirs[is_tri], k * rad[is_tri]) for k in (1.0, 2.0)])
+    c["spheres"] = np.concatenate([small_spheres(c["p"], dirs[~is_tri], k * rad[~is_tri]) for k in (1.0, 2.0)])
+    c["shell"] = 32  # occluders per shell and kind: the first 32 of each kind are the inner shell
+    return c
+
+
+WALL_GAP = 0.05
+WALL_ANG = 0.012
+WALL_SPAN = 0.6  # the lattice spheres are 1 to 1 + WALL_SPAN from P
+
+
+def _case_beside_wall():
+    """P 0.05 from the wall on -x, small spheres (angular radius 0.012) on the lattice around it -- those of
+    384 directions that lie inside the room.  The box reach R0 of such a sphere is mostly the 0x1.6p-10 W term
+    (W: to the far corner of the room, 12 and more); the cone of origins through it ends at a wall a few units
+    on, so the rectangles' reach Rx of k_bin_light_pairs is well below R0.  The face -x sees 0.1 x 0.1 of the
+    wall beside P and nothing else: a seventh camera 0.3 from the wall looks at that patch, and one sphere of the
+    case's own sits between P and the wall and shadows the middle of it (P is within its reach: listed for
+    every direction)."""
+    c = make_case()
+    p = np.array([-HALF + WALL_GAP, P_OFF[1], P_OFF[2]]).astype(F32).astype(float)
+    dirs, rad = lattice(384)
+    s = small_spheres(p, dirs, 1.0 + WALL_SPAN * (rad - 1.0) / 2.0, ang=WALL_ANG)
+    inside = (np.abs(s[:, :3]) + s[:, 3:] < HALF - 0.01).all(axis=1)
+    c["p"], c["lights"], c["spheres"] = p, [p], s[inside]
+    c["extra_spheres"] = np.array([list(p + (-0.025, 0.003, -0.002)) + [0.0143]])
+    foot = (-HALF, p[1], p[2])
+    c["views"] = c["views"] + [(tuple(float(x) for x in np.array([-HALF + 0.3, p[1] + 0.11, p[2] - 0.07], F32)),
+                                tuple(float(x) for x in np.array(foot, F32)))]
+    return c
+
+
 CASES = {
     "triangle cut by face planes": _case_cut_triangle,
     "P nearly in triangles' planes": _case_in_plane,
@@ -343,6 +384,8 @@ CASES = {
     "two lights": lambda: _case_lights(2),
     "five lights": lambda: _case_lights(5),
     "far from the origin": _case_far,
+    "two shells": _case_two_shells,
+    "light beside a wall": _case_beside_wall,
 }
 # what the GPU test expects of the lists: the kinds that have them, and which count must exceed its cap
 # "seen": the case's own primitives are large enough to show in a frame, so some pixels they change are lit;
@@ -354,7 +397,7 @@ for _n in ("triangle cut by face planes", "P nearly in triangles' planes", "P be
            "cell overflow, triangles", "global overflow, triangles", "triangles grouped, spheres not"):
     EXPECT[_n]["sph"] = False
 for _n in ("P inside a sphere's reach", "P inside a sphere", "spheres cut by face planes", "cell overflow, spheres",
-           "global overflow, spheres", "spheres grouped, triangles not"):
+           "global overflow, spheres", "spheres grouped, triangles not", "light beside a wall"):
     EXPECT[_n]["tri"] = False
 for _n in CASES:
     if "overflow" in _n:
@@ -452,3 +495,301 @@ def extras_matter(c, **kw):
         m = (frame(d, v, **kw).view(np.uint32) != frame(d0, v, **kw).view(np.uint32)).any(axis=2)
         out.append((int(m.sum()), int((m & hit & sh).sum()), int((m & hit & ~sh).sum())))
     return out
+
+
+# ---- scenes of their own: a floor under a one-point light, spheres in between ----------------------------------
+def slab_scene(spheres, light=(0.3, 10.0, -0.2), floor_y=-1.5, half=12.0):
+    p = np.asarray(light, np.float32).astype(float)
+    q = np.array([(-half, floor_y, -half), (half, floor_y, -half), (half, floor_y, half), (-half, floor_y, half)])
+    floor = towards(p, q[[0, 1, 2, 0, 2, 3]])
+    grey = ol.material13(ka=(0.6, 0.6, 0.65), kd=(0.6, 0.6, 0.65))
+    geoms = [{"vertex": floor.reshape(-1, 3).astype(np.float32), "face_index": np.arange(6).reshape(2, 3), "material": grey},
+             {"vertex": light_triangles(p).astype(np.float32), "face_index": np.arange(3).reshape(1, 3),
+              "material": ol.LIGHT_A}]
+    s = np.asarray(spheres, np.float32)
+    mats = np.stack([ol.material13(ka=(0.4 + 0.005 * (k % 100), 0.5, 0.8), kd=(0.4 + 0.005 * (k % 100), 0.5, 0.8))
+                     for k in range(len(s))])
+    return ol.scene_dict(geoms, s, mats)
+
+
+SLAB_VIEWS = [((0.5, 3.0, 7.0), (0.0, -1.5, 0.0)), ((-6.0, 2.5, -3.0), (1.0, -1.5, 1.0))]
+
+
+@functools.lru_cache(maxsize=None)
+def far_apart_scene():
+    """80 spheres of radius 0.02 spread thinly over a slab 16 wide, 10 below the light: a k-d leaf of 8
+    spans several units, i.e. tens of cells seen from P"""
+    rng = np.random.default_rng(12)
+    n = 80
+    s = np.stack([rng.uniform(-8, 8, n), rng.uniform(-0.3, 0.3, n), rng.uniform(-8, 8, n), np.full(n, 0.02)], 1)
+    return slab_scene(s)
+
+
+@functools.lru_cache(maxsize=None)
+def overlapping_scene():
+    """64 clusters of two spheres 0.01 apart (original indices 2 k, 2 k + 1) on a jittered 8 x 8 grid of
+    spacing 2: the splits of the k-d order fall between clusters, a leaf's spheres are in index order, so
+    most records hold the two spheres of one cluster -- and seen from P they fill the same cells"""
+    rng = np.random.default_rng(5)
+    s = []
+    for k in range(64):
+        x, z = 2.0 * (k % 8) - 7.0 + rng.uniform(-0.3, 0.3), 2.0 * (k // 8) - 7.0 + rng.uniform(-0.3, 0.3)
+        s += [(x, 0.0, z, 0.15), (x + 0.01, 0.0, z, 0.15)]
+    return slab_scene(np.array(s))
+
+
+def corner_case(lights):
+    """the room's lattice, a light in a corner of the scene box, a sphere so close to it that its reach
+    exceeds half its distance, and one in the direction of the box's far edge"""
+    c = make_case(n_sph=96)
+    corner = np.array([4.5, 4.4, 4.6], np.float32).astype(float)
+    c["lights"] = [corner if q == "corner" else c["p"] for q in lights]
+    c["extra_spheres"] = np.array([list(corner + 0.1 * np.array([-0.6, -0.64, -0.48])) + [0.035],
+                                   list(corner + 0.3 * np.array([-11.0, -10.9, -0.1])) + [0.15]])
+    return c, corner
+
+
+CORNER_ORDERS = [("corner",), ("centre", "corner"), ("corner", "centre")]
+
+
+# ---- the shadow rays the reference traces, and what each of them needs -----------------------------------------
+# A shadow ray of the frame tests the pair records of ONE cell of its light's cube map plus that face's short
+# list (rt_lists.h "Light lists").  A record missing from the cell changes a pixel only where the dropped
+# primitive is the ray's only occluder (the last light) or its first one in index order (an earlier light,
+# through quirk S3).  `needed` does not care: every primitive the reference's any-hit test accepts for the
+# ray with the ray's own initial t counts, whether or not another one would have ended the sweep before it.
+BORDER = 2.0 ** -12  # cells: a ray this close to a cell border is held to both cells (cell_of)
+
+
+def primary_rays(view, size=None):
+    """the reference's primary rays of a view: (origin (3,), dirs (size * size, 3)) fp32, ray h * size + w.
+    camera.h:16-34 through the oracle's own camera (orc_camera_init), get_ray restated one rounding per step"""
+    n = size or W
+    cam = ol.oracle_camera(view[0], view[1], n, n)
+    o, llc, hor, ver = (np.array(list(x), F32) for x in (cam.origin, cam.lower_left_corner, cam.horizontal, cam.vertical))
+    s = (np.arange(n, dtype=F32) / F32(n - 1)).astype(F32)
+    a = (llc[None, None, :] + (hor[None, None, :] * s[None, :, None]).astype(F32)).astype(F32)
+    a = (a + (ver[None, None, :] * s[:, None, None]).astype(F32)).astype(F32)
+    a = (a - o).astype(F32).reshape(-1, 3)
+    return o, ro.normalize(a)
+
+
+def triangles_of(d):
+    """(n, 3, 3) fp32: the scene's triangles by original index (faces geometry by geometry)"""
+    return np.concatenate([g["vertex"][g["face_index"].astype(int)] for g in d["geometry"]]).astype(F32)
+
+
+def accepts(d, o, dirs, tb):
+    """the reference's any-hit tests of rays (o, dirs) with initial t = tb against every primitive
+    -> {"tri": [n_rays, n_tri] bool, "sph": [n_rays, n_sph] bool}, (first acceptor in the reference's order
+    (triangles, then spheres; -1: none), its t2)"""
+    tris, sph = triangles_of(d), d["spheres"]
+    n = len(o)
+    acc = {"tri": np.zeros((n, len(tris)), bool), "sph": np.zeros((n, len(sph)), bool)}
+    first = np.full(n, -1, int)
+    t_first = np.zeros(n, F32)
+    for i, tv in enumerate(tris):
+        ok, t2, _, _ = ro.tri_test(o, dirs, tv[0], tv[1], tv[2])
+        a = ok & ~(t2 >= tb)
+        acc["tri"][:, i] = a
+        new = a & (first < 0)
+        first[new], t_first[new] = i, t2[new]
+    for i, s in enumerate(sph):
+        ok, t2 = ro.sph_test(o, dirs, s)
+        a = ok & ~(t2 >= tb)
+        acc["sph"][:, i] = a
+        new = a & (first < 0)
+        first[new], t_first[new] = len(tris) + i, t2[new]
+    return acc, first, t_first
+
+
+def shadow_rays(d, view, size=None, fixed_face=0):
+    """the shadow rays scan_row traces for a view (oracle/rt_oracle.c scan_row, main.cpp:740-772), for every
+    pixel that hits and every light, in the reference's order (pixel h * size + w, then light):
+        hitp = origin + dir * (t_use - eps);  L = normalize(P - hitp);  tb = length(P - hitp) - eps
+    every step rounded to fp32, P = vertex[fixed_face] + 0 of the light's geometry (quirk S2) and t_use what the
+    light before left in t (quirk S3): the t2 of the first accepting primitive in index order, otherwise its
+    len - eps; the camera's closest t for the first light.
+    -> dict of arrays over the rays: "pixel", "light", "hitp", "L", "tb", "occluded", "facing" (dot(N, L) > 0:
+    an unoccluded light adds to the pixel), and "P" (n_lights, 3), "n_pixels", "origin", "dirs" """
+    o, dirs = primary_rays(view, size)
+    oo = np.broadcast_to(o, dirs.shape)
+    hit, _ = ro.ref_queries(d, oo, dirs)
+    ok = hit["prim"] >= 0
+    pix = np.flatnonzero(ok)
+    hk = {k: v[ok] for k, v in hit.items()}
+    dr = dirs[ok]
+    N, _, has = ro.normals_and_ks(d, hk, np.ascontiguousarray(oo[ok]), dr)
+    assert has.all()
+    lights = d["light_sources"]
+    P = np.array([(d["geometry"][g]["vertex"][fixed_face] + F32(0)).astype(F32) for g in lights], F32).reshape(-1, 3)
+    t = hk["t"].copy()
+    cols = {k: [] for k in ("hitp", "L", "tb", "occluded", "facing")}
+    with np.errstate(all="ignore"):
+        for li in range(len(lights)):
+            hitp = (o + (dr * (t - ro.EPS).astype(F32)[:, None]).astype(F32)).astype(F32)
+            L = (P[li] - hitp).astype(F32)
+            ln = np.sqrt(ro.dot(L, L)).astype(F32)
+            tb = (ln - ro.EPS).astype(F32)
+            L = (L / ln[:, None]).astype(F32)
+            _, first, t_first = accepts(d, hitp, L, tb)
+            occ = first >= 0
+            t = np.where(occ, t_first, tb).astype(F32)
+            for k, v in (("hitp", hitp), ("L", L), ("tb", tb), ("occluded", occ), ("facing", ro.dot(N, L) > 0)):
+                cols[k].append(v)
+    nl = len(lights)
+    out = {k: np.stack(v, axis=1).reshape((len(pix) * nl,) + v[0].shape[1:]) for k, v in cols.items()}
+    out["pixel"] = np.repeat(pix, nl)
+    out["light"] = np.tile(np.arange(nl), len(pix))
+    out.update(P=P, n_pixels=len(dirs), origin=o, dirs=dirs)
+    return out
+
+
+def implied_split(rays):
+    """per pixel, from the restated rays alone -> (hit, sure, maybe): `sure`: the frame with shadows MUST differ
+    from the one without (the first occluded light of the pixel faces the surface: without shadows it adds at
+    least ka / 2 / n_lights, with them nothing, and up to that light both frames took the same steps);
+    `maybe`: some light is occluded.  A frame differs only where `maybe` holds (no occluded light: the same
+    steps throughout).  Between the two lie the pixels whose first occluded light faces away: what it hands on
+    through quirk S3 may or may not change a later light's share; with one light there are none that change."""
+    nl = len(rays["P"])
+    occ = rays["occluded"].reshape(-1, nl)
+    fac = rays["facing"].reshape(-1, nl)
+    pix = rays["pixel"].reshape(-1, nl)[:, 0]
+    k = np.argmax(occ, axis=1)  # the first occluded light, where there is one
+    any_occ = occ.any(axis=1)
+    first_faces = any_occ & fac[np.arange(len(k)), k]
+    hit, sure, maybe = (np.zeros(rays["n_pixels"], bool) for _ in range(3))
+    hit[pix] = True
+    sure[pix], maybe[pix] = first_faces, any_occ
+    if nl == 1:
+        maybe = sure.copy()  # an occluded light that faces away adds nothing either way, and nobody comes after it
+    return hit, sure, maybe
+
+
+def needed(d, rays):
+    """per ray the original primitives whose reference any-hit test accepts it -- ro.tri_test / ro.sph_test and
+    ~(t2 >= tb) with the ray's own initial tb -> {"tri": [n_rays, n_tri] bool, "sph": [n_rays, n_sph] bool}"""
+    with np.errstate(all="ignore"):
+        return accepts(d, rays["hitp"], rays["L"], rays["tb"])[0]
+
+
+def face_axes(face):
+    """(m, ia, ib, sign) of light_face_axes / light_list_cell: the face's axis, the axes of u and w"""
+    m = face >> 1
+    return m, (1 if m == 0 else 0), (1 if m == 2 else 2), (-1.0 if face & 1 else 1.0)
+
+
+def cell_of(P, hitp, R):
+    """light_list_cell (rt_lists.h) restated for rays that start at hitp (n, 3) towards P: v = hitp - P in fp32;
+    the dominant axis exactly as the kernel picks it (strict >, order x, y, z) and the face 2 m + (negative);
+    the coordinates (va / dm + 1) R / 2 in float64.  The kernel divides with v_rcp_f32 (3e-5 cells, it says), so
+    its cell cannot be had bit for bit: a coordinate within BORDER = 2^-12 cells of a cell border stands for
+    both cells -- both binning kernels grow their extents by 1e-3 cells, and 2^-12 + 3e-5 < 1e-3.
+    -> (face (n,), cells (n, 4): index (face R + cw) R + cu within the light, repeated where there is one,
+    u (n,), w (n,))"""
+    v = (np.asarray(hitp, F32) - np.asarray(P, F32)).astype(F32)
+    a = np.abs(v)
+    n = len(v)
+    m = np.zeros(n, int)
+    dm = a[:, 0].copy()
+    for k in (1, 2):
+        g = a[:, k] > dm
+        m[g], dm[g] = k, a[g, k]
+    vm = v[np.arange(n), m]
+    va = np.where(m == 0, v[:, 1], v[:, 0]).astype(np.float64)
+    vb = np.where(m == 2, v[:, 1], v[:, 2]).astype(np.float64)
+    face = 2 * m + (vm < 0)
+    with np.errstate(all="ignore"):
+        u = np.nan_to_num((va / dm.astype(np.float64) + 1.0) * (R / 2.0))
+        w = np.nan_to_num((vb / dm.astype(np.float64) + 1.0) * (R / 2.0))
+
+    def both(x):
+        return [np.clip(np.floor(x + s), 0, R - 1).astype(int) for s in (-BORDER, BORDER)]
+    cells = np.stack([(face * R + cw) * R + cu for cw in both(w) for cu in both(u)], axis=1)
+    return face, cells, u, w
+
+
+def in_box(header, hitp):
+    """shadow_wave_lists' test (rt_kernels.hip): the lists serve a ray only if its origin lies in the grown
+    scene box, fp32 compares against scene_lo / scene_hi = header[4:7] / header[7:10]"""
+    lo, hi = np.asarray(header[4:7], F32), np.asarray(header[7:10], F32)
+    h = np.asarray(hitp, F32)
+    return ((h >= lo) & (h <= hi)).all(axis=1)
+
+
+def sphere_reaches(header, P, centre, r2):
+    """(R0, Rx) of k_bin_light_pairs for one sphere (centre, r2 as the sorted record holds them) and sample
+    point P, in float64 from rt_lists.h's formulas: the box reach and the reach from the cone of origins"""
+    hdr = np.asarray(header, np.float64)
+    g, rho, lo, hi = hdr[0:3], hdr[3], hdr[4:7], hdr[7:10]
+    P, C = np.asarray(P, np.float64), np.asarray(centre, np.float64)
+    k = float.fromhex("0x1.6p-10")
+    delta = 2.0 ** -20 * (rho + np.abs(P - g).sum())
+    far = np.sqrt((np.maximum(np.abs(C - lo), np.abs(C - hi)) ** 2).sum())
+    rad = np.sqrt(max(0.0, float(r2)))
+    R0 = (rad + k * far) * (1.0 + 2.0 ** -20) + delta + 2.0 ** -60
+    c = C - P
+    cn = np.sqrt(c @ c)
+    Rx = R0
+    if ((P >= lo) & (P <= hi)).all() and R0 <= 0.5 * cn:
+        phi0 = np.arcsin(R0 / cn) * (1.0 + 1e-9) + 1e-12
+        s_max = np.inf
+        for a in range(3):
+            e = c[a] / cn
+            room_ = abs(e) * (1.0 - 1e-9) - phi0
+            if room_ > 0.0:
+                s_max = min(s_max, ((hi[a] - P[a] if e > 0.0 else P[a] - lo[a]) + delta) / room_)
+        if np.isfinite(s_max):
+            W1 = (max(cn, s_max - cn) + s_max * phi0) * (1.0 + 1e-9) + delta
+            Rx = (rad + k * min(far, W1)) * (1.0 + 2.0 ** -20) + delta + 2.0 ** -60
+    return R0, Rx
+
+
+_members = {}
+
+
+def members(key, d, view, fixed_face=0):
+    """shadow_rays and needed of one (scene, view), computed once per `key` and left unchanged"""
+    if key not in _members:
+        rays = shadow_rays(d, view, fixed_face=fixed_face)
+        nd = needed(d, rays)
+        for a in list(rays.values()) + list(nd.values()):
+            if isinstance(a, np.ndarray):
+                a.setflags(write=False)
+        _members[key] = (rays, nd)
+    return _members[key]
+
+
+def membership_figures(key, d, views, fixed_face=0, R=128, li=0):
+    """what light li's rays of all the views need, cell by cell (a ray on a border: its lower cell), cached rays:
+      "origins" [6] cells per face that hold a ray origin, "needing" [6] those of them where some ray needs
+      something, "pairs" the distinct needed (cell, kind, primitive) triples, "hidden" those of them reached ONLY
+      by rays that a second primitive accepts as well -- no frame comparison can notice them missing --, "rays"
+      the number of rays of all lights, "inside" [n_lights] the share of each light's rays that start in the scene
+      box (in_box against the scene's header table)"""
+    hdr = ol.scene_to_product(d).table("header").view(F32)
+    origins, needing = [set() for _ in range(6)], [set() for _ in range(6)]
+    every, sole = set(), set()
+    n_rays, nl = 0, len(d["light_sources"])
+    inside, total = np.zeros(nl), np.zeros(nl)
+    for vi, view in enumerate(views):
+        rays, nd = members((key, vi, fixed_face), d, view, fixed_face)
+        n_rays += len(rays["tb"])
+        box = in_box(hdr, rays["hitp"])
+        inside += np.bincount(rays["light"], weights=box, minlength=nl)
+        total += np.bincount(rays["light"], minlength=nl)
+        m = rays["light"] == li
+        face, cells, _, _ = cell_of(rays["P"][li], rays["hitp"][m], R)
+        cell = cells[:, 0]
+        n_acc = nd["tri"][m].sum(axis=1) + nd["sph"][m].sum(axis=1)
+        for f in range(6):
+            origins[f].update(cell[face == f].tolist())
+            needing[f].update(cell[(face == f) & (n_acc > 0)].tolist())
+        for kind in ("tri", "sph"):
+            r, q = np.nonzero(nd[kind][m])
+            every.update(zip(cell[r].tolist(), [kind] * len(r), q.tolist()))
+            alone = n_acc[r] == 1
+            sole.update(zip(cell[r[alone]].tolist(), [kind] * int(alone.sum()), q[alone].tolist()))
+    return {"origins": [len(s) for s in origins], "needing": [len(s) for s in needing], "pairs": every,
+            "hidden": every - sole, "rays": n_rays, "inside": inside / np.maximum(total, 1)}

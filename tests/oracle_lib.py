@@ -105,6 +105,8 @@ def oracle():
                                             C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                             C.POINTER(orc_options), _F, C.POINTER(orc_counters),
                                             C.c_int32]
+        lib.orc_shadow_ray_record.argtypes = [C.POINTER(orc_scene), C.POINTER(orc_camera), C.c_int32, C.c_int32,
+                                              C.POINTER(orc_options), _F]
         lib.orc_quantise.argtypes = [_F, C.c_int64, C.POINTER(C.c_uint8)]
         lib.orc_write_ppm.restype = C.c_int
         lib.orc_write_ppm.argtypes = [C.c_char_p, _F, C.c_int32, C.c_int32]
@@ -373,6 +375,17 @@ def oracle_render(d, lookfrom, lookat, W, H, *, shadows=True, face_mode=ORC_FACE
         return img, {"primary_rays": cnt.primary_rays, "hit_pixels": cnt.hit_pixels,
                      "shadow_rays": cnt.shadow_rays, "anyhit_tests": cnt.anyhit_tests}
     return img
+
+
+def oracle_shadow_rays(d, lookfrom, lookat, W, H, *, fixed_face=0):
+    """orc_shadow_ray_record: (H * W, n_lights, 8) fp32 -- per pixel h * W + w and light {hitp, L, the ray's
+    initial t, 0 no ray / 1 not occluded / 2 occluded}, as scan_row traced them (ORC_FACE_FIXED, every quirk)"""
+    osc = d if isinstance(d, OracleScene) else OracleScene(d)
+    cam = oracle_camera(lookfrom, lookat, W, H)
+    o = orc_options(1, ORC_FACE_FIXED, fixed_face, 0, ORC_QUIRK_ALL)
+    rec = np.zeros((H * W, max(osc.c.n_lights, 1), 8), np.float32)
+    oracle().orc_shadow_ray_record(C.byref(osc.c), C.byref(cam), W, H, C.byref(o), fp(rec))
+    return rec
 
 
 def oracle_render_rows(d, lookfrom, lookat, W, H, rows, *, shadows=True,

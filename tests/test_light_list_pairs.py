@@ -12,7 +12,6 @@ from P, grown by ONE cell on every side (the kernel grows by 1e-3 cells), and th
 face's short list.  The device lists must stay inside that restatement; that they hold every record a ray
 needs is what the frames show: every case renders bit-equal three ways -- lists on, group sweep, CPU oracle.
 """
-import functools
 import math
 
 import numpy as np
@@ -20,6 +19,7 @@ import pytest
 
 import light_list_cases as lc
 import oracle_lib as ol
+from light_list_cases import SLAB_VIEWS, corner_case, far_apart_scene, overlapping_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -171,47 +171,6 @@ def check_inside_restatement(st, x, what):
     return cnt
 
 
-# ---- scenes of their own: a floor under a one-point light, spheres in between ----------------------------------
-def slab_scene(spheres, light=(0.3, 10.0, -0.2), floor_y=-1.5, half=12.0):
-    p = np.asarray(light, np.float32).astype(float)
-    q = np.array([(-half, floor_y, -half), (half, floor_y, -half), (half, floor_y, half), (-half, floor_y, half)])
-    floor = lc.towards(p, q[[0, 1, 2, 0, 2, 3]])
-    grey = ol.material13(ka=(0.6, 0.6, 0.65), kd=(0.6, 0.6, 0.65))
-    geoms = [{"vertex": floor.reshape(-1, 3).astype(np.float32), "face_index": np.arange(6).reshape(2, 3), "material": grey},
-             {"vertex": lc.light_triangles(p).astype(np.float32), "face_index": np.arange(3).reshape(1, 3),
-              "material": ol.LIGHT_A}]
-    s = np.asarray(spheres, np.float32)
-    mats = np.stack([ol.material13(ka=(0.4 + 0.005 * (k % 100), 0.5, 0.8), kd=(0.4 + 0.005 * (k % 100), 0.5, 0.8))
-                     for k in range(len(s))])
-    return ol.scene_dict(geoms, s, mats)
-
-
-SLAB_VIEWS = [((0.5, 3.0, 7.0), (0.0, -1.5, 0.0)), ((-6.0, 2.5, -3.0), (1.0, -1.5, 1.0))]
-
-
-@functools.lru_cache(maxsize=None)
-def far_apart_scene():
-    """80 spheres of radius 0.02 spread thinly over a slab 16 wide, 10 below the light: a k-d leaf of 8
-    spans several units, i.e. tens of cells seen from P"""
-    rng = np.random.default_rng(12)
-    n = 80
-    s = np.stack([rng.uniform(-8, 8, n), rng.uniform(-0.3, 0.3, n), rng.uniform(-8, 8, n), np.full(n, 0.02)], 1)
-    return slab_scene(s)
-
-
-@functools.lru_cache(maxsize=None)
-def overlapping_scene():
-    """64 clusters of two spheres 0.01 apart (original indices 2 k, 2 k + 1) on a jittered 8 x 8 grid of
-    spacing 2: the splits of the k-d order fall between clusters, a leaf's spheres are in index order, so
-    most records hold the two spheres of one cluster -- and seen from P they fill the same cells"""
-    rng = np.random.default_rng(5)
-    s = []
-    for k in range(64):
-        x, z = 2.0 * (k % 8) - 7.0 + rng.uniform(-0.3, 0.3), 2.0 * (k // 8) - 7.0 + rng.uniform(-0.3, 0.3)
-        s += [(x, 0.0, z, 0.15), (x + 0.01, 0.0, z, 0.15)]
-    return slab_scene(np.array(s))
-
-
 def shadowed_pixels(d, view, size):
     on = ol.oracle_render(d, view[0], view[1], size[0], size[1], threads=8)
     off = ol.oracle_render(d, view[0], view[1], size[0], size[1], threads=8, shadows=False)
@@ -317,17 +276,6 @@ def test_pad_half(esc, renderer):
     d, st = room_three_ways(esc, renderer, c, "pad half")
     cnt = check_inside_restatement(st, x, "pad half")
     assert (cnt.reshape(6, -1).max(axis=1) > 0).all()
-
-
-def corner_case(lights):
-    """the room's lattice, a light in a corner of the scene box, a sphere so close to it that its reach
-    exceeds half its distance, and one in the direction of the box's far edge"""
-    c = lc.make_case(n_sph=96)
-    corner = np.array([4.5, 4.4, 4.6], np.float32).astype(float)
-    c["lights"] = [corner if q == "corner" else c["p"] for q in lights]
-    c["extra_spheres"] = np.array([list(corner + 0.1 * np.array([-0.6, -0.64, -0.48])) + [0.035],
-                                   list(corner + 0.3 * np.array([-11.0, -10.9, -0.1])) + [0.15]])
-    return c, corner
 
 
 @pytest.mark.parametrize("lights", [("corner",), ("centre", "corner"), ("corner", "centre")],
