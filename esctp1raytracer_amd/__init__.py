@@ -14,14 +14,14 @@ import numpy as np
 from . import _capi
 from ._capi import (ESC_FACE_FIXED, ESC_FACE_HASH, ESC_STAGE_AUTO, ESC_STAGE_BVH, ESC_STAGE_LDS,
                     ESC_RENDER_EXACT_ONLY, ESC_RENDER_INDEX_ORDER, ESC_RENDER_SHADE_FUSED,
-                    ESC_RENDER_SHADE_QUEUE, ESC_RENDER_TIME_KERNELS, ESC_RENDER_NO_TILE_LISTS, ESC_RENDER_NO_LIGHT_LISTS, ESC_RENDER_TWO_KERNELS, ESC_RENDER_BVH_HEURISTIC_PADS, ESC_RENDER_NO_COUNTERS,
+                    ESC_RENDER_SHADE_QUEUE, ESC_RENDER_TIME_KERNELS, ESC_RENDER_NO_TILE_LISTS, ESC_RENDER_NO_LIGHT_LISTS, ESC_RENDER_TWO_KERNELS, ESC_RENDER_BVH_HEURISTIC_PADS, ESC_RENDER_NO_COUNTERS, ESC_RENDER_NO_PACKED_LIGHT_LISTS,
                     ESC_STAGE_SMEM, ESC_TRANSMIT_OFF, ESC_TRANSMIT_REFRACT, ESC_TRANSMIT_FRESNEL, EscError,
                     check)
 
 __all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "live_device_allocations", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table", "environment_sky", "environment_lookup_host",
            "EscError", "ESC_FACE_FIXED", "ESC_FACE_HASH", "ESC_STAGE_AUTO", "ESC_STAGE_SMEM",
            "ESC_STAGE_LDS", "ESC_STAGE_BVH", "ESC_RENDER_EXACT_ONLY", "ESC_RENDER_TIME_KERNELS", "ESC_RENDER_INDEX_ORDER", "ESC_RENDER_SHADE_QUEUE",
-           "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "ESC_TRANSMIT_OFF", "ESC_TRANSMIT_REFRACT", "ESC_TRANSMIT_FRESNEL", "version"]
+           "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "ESC_RENDER_NO_PACKED_LIGHT_LISTS", "ESC_TRANSMIT_OFF", "ESC_TRANSMIT_REFRACT", "ESC_TRANSMIT_FRESNEL", "version"]
 
 
 def _f32(a, shape=None):
@@ -1138,6 +1138,28 @@ class Renderer:
         return {"n_listed": n_listed, "R": R, "cap": cap, "global_cap": gcap,
                 "point": np.array(list(info[4:4 + n_listed]), np.int32), "face_counts": face_counts,
                 "face_ids": face_ids, "counts": counts.reshape(n_listed, 6, R, R), "ids": ids}
+
+    def light_lists_packed(self):
+        """esc_light_list_packed_read: the packed form of the sphere light lists of the last frame, the
+        form the shadow sweep reads, or None when there is none -> dict: "n_listed", "R", "per_step" (4),
+        "total_steps", "steps" (n_listed, 6, R, R) indexed [light, face, cw, cu], -1 for a cell over its
+        list capacity, and "slots" (n_listed, 6, R, R, 2 * list capacity): a cell's 4 * steps slots in the
+        order they are tested, each a position 2 j + h in the group-sorted table or -1 (pad), then -1"""
+        info = (C.c_int32 * 8)()
+        i32 = C.POINTER(C.c_int32)
+        n = check(self._lib.esc_light_list_packed_read(self._h, info, 0, 0, None, None))
+        if n == 0:
+            return None
+        n_listed, R, per_cell = info[0], info[1], info[2]
+        per_light = 6 * R * R
+        steps = np.zeros((n_listed, 6, R, R), np.int32)
+        slots = np.zeros((n_listed, 6, R, R, per_cell), np.int32)
+        for li in range(n_listed):  # one copy per light
+            check(self._lib.esc_light_list_packed_read(self._h, info, li * per_light, per_light,
+                                                       steps[li].ctypes.data_as(i32),
+                                                       slots[li].ctypes.data_as(i32)))
+        return {"n_listed": n_listed, "R": R, "per_step": info[3], "total_steps": info[4],
+                "steps": steps, "slots": slots}
 
 
 class RecordedFrame:

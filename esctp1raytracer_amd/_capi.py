@@ -41,6 +41,7 @@ ESC_RENDER_NO_LIGHT_LISTS = 64
 ESC_RENDER_TWO_KERNELS = 128
 ESC_RENDER_BVH_HEURISTIC_PADS = 256
 ESC_RENDER_NO_COUNTERS = 512
+ESC_RENDER_NO_PACKED_LIGHT_LISTS = 1024
 # ESC_TABLE_*: the index of a name is its value
 ESC_TABLE_NAMES = ("tri", "tri_n", "sph", "sph_mat", "mat", "transmit", "lights", "light_points",
                    "sph2", "sph2_f", "sph2_ord", "sph2_f_ord", "tri2_f", "tri2_pf",
@@ -237,6 +238,7 @@ SIGNATURES = {
     "esc_tile_list_counts": (C.c_int, [C.c_void_p, C.c_int32, _I32, _I32, C.c_size_t]),
     "esc_tile_list_ids": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, _I32, C.c_int32]),
     "esc_light_list_read": (C.c_int, [C.c_void_p, C.c_int32, _I32, _I32, _I32, C.c_int64, C.c_int64, _I32]),
+    "esc_light_list_packed_read": (C.c_int, [C.c_void_p, _I32, C.c_int64, C.c_int64, _I32, _I32]),
     "esc_tile_rect": (C.c_int, [C.POINTER(esc_camera), C.c_int32, C.c_int32, _F, C.c_double, _I32]),
     "esc_tile_band": (C.c_int, [C.POINTER(esc_camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F,
                                 C.c_double]),

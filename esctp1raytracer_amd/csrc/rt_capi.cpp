@@ -42,6 +42,7 @@ extern "C" int esc_launch_prepare_bvh(const esc::DevTri *tri, esc::DevTriP *tri_
                                       float ox, float oy, float oz, hipStream_t stream);
 extern "C" int esc_launch_tile_lists(const esc::RenderParams *p, hipStream_t stream);
 extern "C" int esc_launch_light_lists(const esc::RenderParams *p, hipStream_t stream);
+extern "C" int esc_launch_light_pack(const esc::RenderParams *p, int fill, hipStream_t stream);
 extern "C" int esc_launch_bin_primary(const esc::RenderParams *p, const esc::PrimBoxDev *tri_boxes,
                                       const esc::PrimBoxDev *sph_boxes, hipStream_t stream);
 extern "C" int esc_launch_bin_light(const esc::LightBins *g, const float *light_points,
@@ -147,6 +148,8 @@ struct esc_context {
   // light lists of the shadow pass (rt_device.h LightLists), valid for (scene, ll_face_mode, ll_fixed_face)
   esc::LightLists ll{}, lt{}; // sphere / triangle pair records
   int ll_alloc_lights = 0;
+  size_t ll_pk_steps_cap = 0; // steps ll.pk_rec / ll.pk_pos hold (the spare step not counted)
+  int32_t ll_pk_steps = -1;   // steps the packed cells of the valid lists use; < 0: not built for them
   int ll_face_mode = -1, ll_fixed_face = -1;
   bool ll_valid = false;
   std::vector<esc::DevLight> h_lights;
@@ -1029,6 +1032,8 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
           if ((rc = ctx->frame.alloc(L->ids, cells * esc::kLightListCap))) return rc;
         }
         if ((rc = ctx->frame.alloc(ctx->lt.esc, (size_t)n_listed * esc::kLightEscCap))) return rc;
+        if ((rc = ctx->frame.alloc(ctx->ll.pk_cell, cells))) return rc;
+        if (!ctx->ll.pk_total && (rc = ctx->frame.alloc(ctx->ll.pk_total, 1))) return rc;
         ctx->ll_alloc_lights = n_listed;
         ctx->ll_valid = false;
       }
@@ -1042,9 +1047,10 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
                         (opts->face_mode == ESC_FACE_FIXED ? opts->fixed_face : 0);
         (src == &ctx->ll ? p.ll : p.lt) = L;
       }
-      if (!ctx->ll_valid || ctx->ll_face_mode != opts->face_mode ||
-          (opts->face_mode == ESC_FACE_FIXED && ctx->ll_fixed_face != opts->fixed_face) ||
-          ctx->ll.n_listed != n_listed) {
+      const bool rebuild = !ctx->ll_valid || ctx->ll_face_mode != opts->face_mode ||
+                           (opts->face_mode == ESC_FACE_FIXED && ctx->ll_fixed_face != opts->fixed_face) ||
+                           ctx->ll.n_listed != n_listed;
+      if (rebuild) {
         for (const esc::LightLists *L : {&p.ll, &p.lt}) {
           HIP_TRY(hipMemsetAsync(L->hdr, 0, (size_t)n_listed * 6 * esc::kTileHdrInts * 4, ctx->stream));
           HIP_TRY(hipMemsetAsync(L->cnt, 0, cells * 4, ctx->stream));
@@ -1056,6 +1062,40 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
           set_error(std::string("k_bin_light_* launch: ") + hipGetErrorString((hipError_t)e));
           return ESC_ERR_HIP;
         }
+        // the packed form of the sphere lists: count, size the stream exactly (one read-back per scene
+        // and sample point; this path never runs inside a capture), fill
+        ctx->ll_pk_steps = -1;
+        if (p.ll.enabled) {
+          HIP_TRY(hipMemsetAsync(p.ll.pk_total, 0, 4, ctx->stream));
+          if ((e = esc_launch_light_pack(&p, 0, ctx->stream))) {
+            set_error(std::string("k_pack_light_cells launch: ") + hipGetErrorString((hipError_t)e));
+            return ESC_ERR_HIP;
+          }
+          HIP_TRY(hipStreamSynchronize(ctx->stream));
+          int32_t steps = 0;
+          HIP_TRY(hipMemcpy(&steps, p.ll.pk_total, 4, hipMemcpyDeviceToHost));
+          if (steps < 0) {
+            set_error("k_pack_light_cells: the packed light lists do not fit 2^31 steps");
+            return ESC_ERR_HIP;
+          }
+          if (!ctx->ll.pk_rec || (size_t)steps > ctx->ll_pk_steps_cap) {
+            int rc;
+            ctx->ll_pk_steps_cap = 0;
+            if ((rc = ctx->frame.alloc(ctx->ll.pk_rec, 2 * (size_t)steps + 2))) return rc;
+            if ((rc = ctx->frame.alloc(ctx->ll.pk_pos, 4 * (size_t)steps + 4))) return rc;
+            ctx->ll_pk_steps_cap = (size_t)steps;
+            p.ll.pk_rec = ctx->ll.pk_rec;
+            p.ll.pk_pos = ctx->ll.pk_pos;
+          }
+          // (the spare step at the end of the stream, and whatever a shorter stream leaves: pad halves
+          // need no writing -- nothing read past a cell's steps is ever tested)
+          HIP_TRY(hipMemsetAsync(p.ll.pk_rec + 2 * (size_t)steps, 0, 2 * sizeof(esc::DevSphPair), ctx->stream));
+          if ((e = esc_launch_light_pack(&p, 1, ctx->stream))) {
+            set_error(std::string("k_pack_light_cells launch: ") + hipGetErrorString((hipError_t)e));
+            return ESC_ERR_HIP;
+          }
+          ctx->ll_pk_steps = steps;
+        }
         ctx->ll.n_listed = ctx->lt.n_listed = n_listed;
         ctx->ll.R = ctx->lt.R = Rr;
         std::memcpy(ctx->ll.point, p.ll.point, sizeof(p.ll.point)); // (for esc_light_list_read)
@@ -1065,6 +1105,8 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
         ctx->ll_valid = true;
         ctx->epoch++;
       }
+      // the A/B switch: the consumer sweeps the id lists when it gets no packed cells
+      if ((opts->flags & ESC_RENDER_NO_PACKED_LIGHT_LISTS) || !p.ll.enabled || ctx->ll_pk_steps < 0) p.ll.pk_cell = nullptr;
     }
   }
   int stage = (eff_stage == ESC_STAGE_LDS) ? 2 : 1; // AUTO -> SMEM (measured)
@@ -1515,6 +1557,48 @@ int esc_light_list_read(esc_context *ctx, int32_t which, int32_t info[8], int32_
     for (int64_t c = 0; c < n_cells; c++) // slots past a cell's count hold stale (valid) records: not stored ids
       for (int k = std::max(0, std::min(cnt[(size_t)c], (int32_t)esc::kLightListCap)); k < esc::kLightListCap; k++)
         cell_ids[(size_t)c * esc::kLightListCap + k] = -1;
+  }
+  return (int)total;
+}
+
+int esc_light_list_packed_read(esc_context *ctx, int32_t info[8], int64_t first_cell, int64_t n_cells,
+                               int32_t *steps, int32_t *slots) {
+  if (!ctx || !info || first_cell < 0 || n_cells < 0) {
+    set_error("esc_light_list_packed_read: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  const esc::LightLists &L = ctx->ll;
+  if (!ctx->ll_valid || !L.hdr || !L.pk_cell || !L.pk_pos || ctx->ll_pk_steps < 0 || ctx->sg.n_grp == 0) return 0;
+  const int64_t total = (int64_t)L.n_listed * 6 * L.R * L.R;
+  if (first_cell > total || n_cells > total - first_cell) {
+    set_error("esc_light_list_packed_read: cells out of range");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const int32_t per_cell = 2 * esc::kLightListCap;
+  const int32_t out[8] = {L.n_listed, L.R, per_cell, 4, ctx->ll_pk_steps, 0, 0, 0};
+  std::memcpy(info, out, sizeof(out));
+  if ((steps || slots) && n_cells > 0) {
+    std::vector<esc::LightCell> cells((size_t)n_cells);
+    HIP_TRY(hipMemcpy(cells.data(), L.pk_cell + first_cell, (size_t)n_cells * sizeof(esc::LightCell),
+                      hipMemcpyDeviceToHost));
+    std::vector<int32_t> pos;
+    if (slots && ctx->ll_pk_steps > 0) {
+      pos.resize(4 * (size_t)ctx->ll_pk_steps);
+      HIP_TRY(hipMemcpy(pos.data(), L.pk_pos, pos.size() * 4, hipMemcpyDeviceToHost));
+    }
+    for (int64_t c = 0; c < n_cells; c++) {
+      const esc::LightCell ce = cells[(size_t)c];
+      if (steps) steps[c] = ce.n_steps < 0 ? -1 : ce.n_steps;
+      if (!slots) continue;
+      int32_t *row = slots + (size_t)c * per_cell;
+      const bool ok = ce.n_steps > 0 && ce.offset >= 0 && 4 * (int64_t)ce.n_steps <= per_cell &&
+                      (int64_t)ce.offset + ce.n_steps <= (int64_t)ctx->ll_pk_steps;
+      const int m = ok ? 4 * ce.n_steps : 0;
+      for (int k = 0; k < m; k++) row[k] = pos[4 * (size_t)ce.offset + k];
+      for (int k = m; k < per_cell; k++) row[k] = -1;
+    }
   }
   return (int)total;
 }

@@ -324,6 +324,9 @@ struct alignas(16) LightEsc { // |v . n| <= kp over a cell's directions v = +-e_
   float nx, ny, nz, kp;
   int32_t pair, pad[3];
 };
+struct alignas(8) LightCell {
+  int32_t offset, n_steps;
+};
 struct LightLists {
   int32_t *hdr;  // [n_listed * 6][kTileHdrInts]: [0] face-global pair records, [1] (face 0 of a light:)
                  // its LightEsc entries, [2] off, [8..) the face-global ids
@@ -334,6 +337,13 @@ struct LightLists {
   int32_t R;
   int32_t point[kLightListMax];
   int32_t enabled, pad;
+  // The PACKED form the shadow sweep reads (sphere lists only; rt_lists.h "Packed cells"), derived from
+  // cnt / ids once they are sorted: per cell the spheres -- halves of its records -- whose own
+  // rectangle holds the cell, as copies of their constants, in steps of 4 spheres = 2 pair records.
+  LightCell *pk_cell;  // [cells]: where the cell's steps start and how many (n_steps < 0: over the cap)
+  DevSphPair *pk_rec;  // [2 * steps + 2]: the steps of all cells, back to back; spare slots are pad halves
+  int32_t *pk_pos;     // [4 * steps]: every slot's position 2 j + h in the sorted table (-1: pad)
+  int32_t *pk_total;   // [1]: steps handed out (k_pack_light_cells<false>)
 };
 
 // hand-over between k_primary and k_shade: the closest hit of every pixel of the band

@@ -731,7 +731,7 @@ constexpr int kTriListServed = 0x20000000; // ... its triangle phase did
 // per-pixel shading state, which is parked in LDS while the sweeps run so that it holds no VGPRs
 // across them.  All 256 threads must call it (barriers inside).
 // ---------------------------------------------------------------------------------------
-template <bool TGRP>
+template <bool TGRP, bool IDL>
 DEVINL void shadow_sweep_smem(const RenderParams &p, RepackLds &R, int tid, int wave, int lane, int li, f3 ro,
                               f3 &rL, Any (&a)[1], f3 &N, float &r, float &g, float &b, float &t, int &mi,
                               int &grp_open, bool &tri_groups, bool &sph_groups, int &n_swept) {
@@ -815,7 +815,7 @@ DEVINL void shadow_sweep_smem(const RenderParams &p, RepackLds &R, int tid, int 
               SmemFetch<TriPairF>{reinterpret_cast<const TriPairF *>(p.tg.sorted2_f)},
               SmemFetch<DevTri>{p.tg.sorted}, 0, so, sL, rt, aa, n_tests, sw);
           n_swept += sw;
-          if (rr >= 0) R.n_open[rr] = (R.n_open[rr] + (n_tests >> 3)) | (served ? kTriListServed : 0);
+          if (rr >= 0) R.n_open[rr] = (R.n_open[rr] + (n_tests >> 2)) | (served ? kTriListServed : 0);
         }
         if (!served) {
         // k0 sorted slots in = k0 / 8 groups = k0 / kPerSup super-groups = k0 / kPerHyp hyper-groups;
@@ -832,7 +832,7 @@ DEVINL void shadow_sweep_smem(const RenderParams &p, RepackLds &R, int tid, int 
             SmemFetch<DevTri>{p.tg.sorted + k0}, n_here / kPerHyp, k0, so, sL, rs,
             rt, far, aa,
             n_open);
-        if (rr >= 0 && n_open) R.n_open[rr] += n_open;
+        if (rr >= 0 && n_open) R.n_open[rr] += 2 * n_open;
         }
       } else if (in_tris) {
         const V3<V> sov[1] = {{so.x, so.y, so.z}}, sLv[1] = {{sL.x, sL.y, sL.z}};
@@ -868,12 +868,12 @@ DEVINL void shadow_sweep_smem(const RenderParams &p, RepackLds &R, int tid, int 
             __builtin_amdgcn_ballot_w64(aa[0].tb > 0.f && outside) == 0) {
           const f3 Pl = ld3(p.light_points + 4 * p.ll.point[li]);
           int n_tests = 0, sw = 0;
-          served = anyhit_sph_light_lists(
+          served = anyhit_sph_light_lists<IDL>(
               p.ll, light_list_cell(p.ll, li, Pl, so),
               SmemFetch<PairG>{reinterpret_cast<const PairG *>(p.sg.sorted2)}, p.n_tri, so, sL, aa[0],
               n_tests, sw);
           n_swept += sw;
-          if (rr >= 0) R.n_open[rr] = (R.n_open[rr] + (n_tests >> 3)) | (served ? kListServed : 0);
+          if (rr >= 0) R.n_open[rr] = (R.n_open[rr] + (n_tests >> 2)) | (served ? kListServed : 0);
         }
         if (!served)
         // k0 pair records in = k0 / 4 groups = k0 / 32 super-groups = k0 / 256 hyper-groups; two per record
@@ -885,7 +885,7 @@ DEVINL void shadow_sweep_smem(const RenderParams &p, RepackLds &R, int tid, int 
             SmemFetch<PairF>{reinterpret_cast<const PairF *>(p.sg.sorted2_f) + k0},
             SmemFetch<PairG>{reinterpret_cast<const PairG *>(p.sg.sorted2) + k0}, n_here >> 8,
             p.n_tri + 2 * k0, so, sL, rf, far, aa[0], n_open);
-        if (rr >= 0 && n_open) R.n_open[rr] += n_open;
+        if (rr >= 0 && n_open) R.n_open[rr] += 2 * n_open;
       } else if (p.use_filter) {
         const RayF rf = make_ray_filter(so, sL, p.shadow_center);
         n_swept += 2 * anyhit_sph_pairs_filter(
@@ -961,7 +961,7 @@ template <bool TGRP> DEVINL bool shadow_lists_cover(const RenderParams &p, int l
 // false: some live ray of this wave cannot be served (it starts outside the region the lists were
 // built for, or its cell overflowed) -- the caller runs shadow_sweep_smem for the workgroup with
 // the untouched `a`.  true: a.kocc / a.tocc hold what the sweep would have reported.
-template <bool TGRP>
+template <bool TGRP, bool IDL>
 DEVINL bool shadow_wave_lists(const RenderParams &p, int li, f3 so, f3 sL, Any &a, int &grp_open,
                               bool &tri_groups, bool &sph_groups, int &n_swept) {
   const bool last_light = li == p.n_lights - 1;
@@ -999,7 +999,7 @@ DEVINL bool shadow_wave_lists(const RenderParams &p, int li, f3 so, f3 sL, Any &
                                   SmemFetch<DevTri>{p.tg.sorted}, 0, so, sL, rt, aa, n_tests, sw))
         return false;
       sw_all += sw;
-      if (tb > 0.f) n_open = (n_open + (n_tests >> 3)) | kTriListServed;
+      if (tb > 0.f) n_open = (n_open + (n_tests >> 2)) | kTriListServed;
     } else if (__builtin_amdgcn_ballot_w64(tb > 0.f) != 0) {
       const V3<float> sov[1] = {{so.x, so.y, so.z}}, sLv[1] = {{sL.x, sL.y, sL.z}};
       sw_all += p.n_tri;
@@ -1025,12 +1025,12 @@ DEVINL bool shadow_wave_lists(const RenderParams &p, int li, f3 so, f3 sL, Any &
     if (__builtin_amdgcn_ballot_w64(tb > 0.f && !in_box) != 0) return false;
     const f3 Pl = ld3(p.light_points + 4 * p.ll.point[li]);
     int n_tests = 0, sw = 0;
-    if (!anyhit_sph_light_lists(p.ll, light_list_cell(p.ll, li, Pl, so),
+    if (!anyhit_sph_light_lists<IDL>(p.ll, light_list_cell(p.ll, li, Pl, so),
                                 SmemFetch<PairG>{reinterpret_cast<const PairG *>(p.sg.sorted2)}, p.n_tri, so, sL,
                                 aa, n_tests, sw))
       return false;
     sw_all += sw;
-    if (tb > 0.f) n_open = (n_open + (n_tests >> 3)) | kListServed;
+    if (tb > 0.f) n_open = (n_open + (n_tests >> 2)) | kListServed;
     if (aa.kocc >= 0) {
       out.tocc = aa.tocc;
       out.kocc = aa.kocc;
@@ -1048,7 +1048,7 @@ DEVINL bool shadow_wave_lists(const RenderParams &p, int li, f3 so, f3 sL, Any &
   return true;
 }
 
-template <int STAGE, bool TGRP = false>
+template <int STAGE, bool TGRP = false, bool IDL = false>
 __global__ void __launch_bounds__(256, STAGE == STAGE_LDS ? 4 : (TGRP ? 5 : 6)) k_shade(const RenderParams p) {
   typedef float V;
   constexpr int NV = 1;
@@ -1140,7 +1140,7 @@ __global__ void __launch_bounds__(256, STAGE == STAGE_LDS ? 4 : (TGRP ? 5 : 6)) 
   for (int li = 0; li < p.n_lights; ++li) {
     const DevLight Lt = p.lights[li];
     Any a[1];
-    int grp_open = 0; // 8-record openings of group sweeps this ray needed (counters only)
+    int grp_open = 0; // tests of group openings (8 each) and list steps (4 or 8) this ray needed, in units of 4 (counters only)
     bool tri_groups = false, sph_groups = false; // this light swept triangle / sphere groups
     uint32_t cnt_lane = 0;                       // this ray's any-hit tests for this light
     f3 ro = N, rL = N; // shadow-ray origin (main.cpp:757 `hit`) and unit direction
@@ -1212,7 +1212,7 @@ __global__ void __launch_bounds__(256, STAGE == STAGE_LDS ? 4 : (TGRP ? 5 : 6)) 
           Any af = a[0];
           int go = 0, sw = 0;
           bool tg = false, sgp = false;
-          const bool ok = shadow_wave_lists<TGRP>(p, li, ro, rL, af, go, tg, sgp, sw);
+          const bool ok = shadow_wave_lists<TGRP, IDL>(p, li, ro, rL, af, go, tg, sgp, sw);
           if (!wg_vote_any(vote_word, vote_k, !ok)) {
             a[0].kocc = af.kocc;
             a[0].tocc = af.tocc;
@@ -1224,7 +1224,7 @@ __global__ void __launch_bounds__(256, STAGE == STAGE_LDS ? 4 : (TGRP ? 5 : 6)) 
           }
         }
         if (!served)
-          shadow_sweep_smem<TGRP>(p, lds_rays, tid, wave, lane, li, ro, rL, a, N, r, g, b, t, mi, grp_open,
+          shadow_sweep_smem<TGRP, IDL>(p, lds_rays, tid, wave, lane, li, ro, rL, a, N, r, g, b, t, mi, grp_open,
                                   tri_groups, sph_groups, n_swept);
       } else {
         const V3<V> ov[1] = {{ro.x, ro.y, ro.z}}, Lv[1] = {{rL.x, rL.y, rL.z}};
@@ -1262,11 +1262,11 @@ __global__ void __launch_bounds__(256, STAGE == STAGE_LDS ? 4 : (TGRP ? 5 : 6)) 
                              : tri_groups ? (unsigned)(by_tri ? k / (kTriGroup * kTriSuper * kTriHyper) + 1
                                                               : p.tg.n_hyp)
                                           : (unsigned)(by_tri ? k + 1 : p.n_tri);
-          // (a ray its light's lists served: the 8-sphere batches it was live for, nothing else)
+          // (a ray its light's lists served: the 4-sphere steps / 8-sphere batches it was live for, nothing else)
           if (!by_tri && !(grp_open & kListServed))
             cnt += sph_groups ? (unsigned)(k >= 0 ? ((k - p.n_tri) >> 9) + 1 : p.sg.n_hyp)
                               : (unsigned)(k >= 0 ? k - p.n_tri + 1 : p.n_sph);
-          cnt_lane = cnt + 8u * (unsigned)(grp_open & ~(kListServed | kTriListServed));
+          cnt_lane = cnt + 4u * (unsigned)(grp_open & ~(kListServed | kTriListServed));
         }
       }
       if (p.shadows && a[0].kocc >= 0) {
@@ -1348,7 +1348,7 @@ DEVINL void emit_counters_n(const RenderParams &p, int tid, int lane, uint32_t n
     atomicAdd(&p.counters[(blockIdx.x % kCounterSets) * 8 + tid], wg_cnt[tid]);
 }
 
-template <bool GRP, bool TGRP>
+template <bool GRP, bool TGRP, bool IDL = false>
 __global__ void __launch_bounds__(256, TGRP ? 4 : 5) k_frame(const RenderParams p) {
   __shared__ RepackLds lds_rays;
   __shared__ float park[2][6][256]; // per pixel q of thread t: dir xyz, t, v, idx
@@ -1460,7 +1460,7 @@ __global__ void __launch_bounds__(256, TGRP ? 4 : 5) k_frame(const RenderParams 
           Any af = a[0];
           int go = 0, sw = 0;
           bool tg = false, sgp = false;
-          const bool ok = shadow_wave_lists<TGRP>(p, li, ro, rL, af, go, tg, sgp, sw);
+          const bool ok = shadow_wave_lists<TGRP, IDL>(p, li, ro, rL, af, go, tg, sgp, sw);
           if (!wg_vote_any(vote_word, vote_k, !ok)) { // every wave of the workgroup was served
             a[0].kocc = af.kocc;
             a[0].tocc = af.tocc;
@@ -1472,7 +1472,7 @@ __global__ void __launch_bounds__(256, TGRP ? 4 : 5) k_frame(const RenderParams 
           }
         }
         if (!served)
-          shadow_sweep_smem<TGRP>(p, lds_rays, tid, wave, lane, li, ro, rL, a, N, r, g, b, t, mi, grp_open,
+          shadow_sweep_smem<TGRP, IDL>(p, lds_rays, tid, wave, lane, li, ro, rL, a, N, r, g, b, t, mi, grp_open,
                                   tri_groups, sph_groups, n_swept);
       }
       if (has_hit) {
@@ -1488,7 +1488,7 @@ __global__ void __launch_bounds__(256, TGRP ? 4 : 5) k_frame(const RenderParams 
           if (!by_tri && !(grp_open & kListServed))
             cnt += sph_groups ? (unsigned)(k >= 0 ? ((k - p.n_tri) >> 9) + 1 : p.sg.n_hyp)
                               : (unsigned)(k >= 0 ? k - p.n_tri + 1 : p.n_sph);
-          cnt_lane = cnt + 8u * (unsigned)(grp_open & ~(kListServed | kTriListServed));
+          cnt_lane = cnt + 4u * (unsigned)(grp_open & ~(kListServed | kTriListServed));
         }
         if (p.shadows && a[0].kocc >= 0) {
           t = a[0].tocc; // occlusion() wrote the occluder's t2 through its reference (quirk S3)
@@ -1881,6 +1881,18 @@ extern "C" int esc_launch_light_lists(const esc::RenderParams *p, hipStream_t st
   return (int)hipGetLastError();
 }
 
+// the packed form of the sorted sphere light lists (rt_lists.h "Packed cells"): fill == 0 counts and hands
+// out the offsets (pk_total zeroed by the caller on this stream), fill == 1 writes pk_rec / pk_pos
+extern "C" int esc_launch_light_pack(const esc::RenderParams *p, int fill, hipStream_t stream) {
+  const int n_cells = p->ll.n_listed * 6 * p->ll.R * p->ll.R;
+  if (n_cells <= 0) return 0;
+  if (fill)
+    hipLaunchKernelGGL(esc::k_pack_light_cells<true>, dim3((n_cells + 255) / 256), dim3(256), 0, stream, *p);
+  else
+    hipLaunchKernelGGL(esc::k_pack_light_cells<false>, dim3((n_cells + 255) / 256), dim3(256), 0, stream, *p);
+  return (int)hipGetLastError();
+}
+
 extern "C" int esc_launch_bin_primary(const esc::RenderParams *p, const esc::PrimBoxDev *tri_boxes,
                                       const esc::PrimBoxDev *sph_boxes, hipStream_t stream) {
   const int n = p->n_tri + p->n_sph;
@@ -1987,6 +1999,13 @@ extern "C" int esc_launch_render(const esc::RenderParams *p, int stage, int px, 
   using esc::v2f;
   const int tiles_y = (p->n_local_rows + esc::kTileH - 1) / esc::kTileH;
   const int shade_grid = ((p->W + 31) / 32) * tiles_y;
+  // The instantiations whose sphere-list loop reads packed cells run only when there are packed cells.
+  // Everything else -- ESC_RENDER_NO_PACKED_LIGHT_LISTS, and frames without sphere light lists at all
+  // (no shadows, no spheres: c2, c5), where that loop never runs -- takes the id-list instantiations,
+  // the kernels as they were before the packed form.  (Both loops in one kernel cost k_frame<true, true>
+  // a wave per SIMD; the packed instantiation alone allocates its registers differently and measured
+  // 1 % slower on c5, which has no use for it.)
+  const bool idl = !(p->use_filter && p->ll.enabled && p->sg.n_grp > 0 && p->ll.pk_cell != nullptr);
   if (stage == esc::STAGE_BVH) { // one kernel: closest hit + shading
     hipLaunchKernelGGL((esc::k_shade<esc::STAGE_BVH>), dim3(shade_grid), dim3(256), 0, stream, *p);
   } else if (stage == esc::STAGE_LDS) {
@@ -1999,17 +2018,25 @@ extern "C" int esc_launch_render(const esc::RenderParams *p, int stage, int px, 
     const dim3 grid((unsigned)((p->W + 63) / 64), (unsigned)tiles_y); // (x, y) = the tile: Tile<2>::Grid2D
     const bool grp = p->use_filter && (p->sg.n_grp > 0 || p->tg.n_grp > 0);
     const bool tgrp = p->use_filter && p->tg.n_grp > 0;
-    if (tgrp)
+    if (tgrp && idl)
+      hipLaunchKernelGGL((esc::k_frame<true, true, true>), grid, dim3(256), 0, stream, *p);
+    else if (tgrp)
       hipLaunchKernelGGL((esc::k_frame<true, true>), grid, dim3(256), 0, stream, *p);
+    else if (grp && idl)
+      hipLaunchKernelGGL((esc::k_frame<true, false, true>), grid, dim3(256), 0, stream, *p);
     else if (grp)
       hipLaunchKernelGGL((esc::k_frame<true, false>), grid, dim3(256), 0, stream, *p);
-    else
-      hipLaunchKernelGGL((esc::k_frame<false, false>), grid, dim3(256), 0, stream, *p);
+    else // (no groups: no light lists)
+      hipLaunchKernelGGL((esc::k_frame<false, false, true>), grid, dim3(256), 0, stream, *p);
   } else {
     launch_primary<esc::STAGE_SMEM, v2f, 1>(p, stream); // always 2 px: see esc_launch_primary_only
     if (between) (void)hipEventRecord(between, stream);
-    if (p->use_filter && p->tg.n_grp > 0)
+    if (p->use_filter && p->tg.n_grp > 0 && idl)
+      hipLaunchKernelGGL((esc::k_shade<esc::STAGE_SMEM, true, true>), dim3(shade_grid), dim3(256), 0, stream, *p);
+    else if (p->use_filter && p->tg.n_grp > 0)
       hipLaunchKernelGGL((esc::k_shade<esc::STAGE_SMEM, true>), dim3(shade_grid), dim3(256), 0, stream, *p);
+    else if (idl)
+      hipLaunchKernelGGL((esc::k_shade<esc::STAGE_SMEM, false, true>), dim3(shade_grid), dim3(256), 0, stream, *p);
     else
       hipLaunchKernelGGL((esc::k_shade<esc::STAGE_SMEM>), dim3(shade_grid), dim3(256), 0, stream, *p);
   }

@@ -308,7 +308,13 @@ enum {
    * workgroup and a wave reduction per light and pixel: 9 % of a c4 frame.  Every frame of a fixed
    * scene, camera and option set counts the same rays, so a caller that wants both (bench.py) counts
    * one frame and times the others. */
-  ESC_RENDER_NO_COUNTERS = 512
+  ESC_RENDER_NO_COUNTERS = 512,
+  /* The shadow sweep reads the sphere light lists in a packed form derived from them: per cell only the
+   * spheres whose own rectangle holds the cell, as copies of their constants, four per step (DESIGN.md
+   * 3.9).  This flag makes it sweep the lists of pair-record ids instead, as before the packed form
+   * existed -- the same image bit for bit, more tests: the A/B switch, and what the tests compare
+   * against.  The lists themselves (esc_light_list_read) are the same either way. */
+  ESC_RENDER_NO_PACKED_LIGHT_LISTS = 1024
 };
 
 typedef struct {
@@ -544,6 +550,18 @@ int esc_tile_list_ids(esc_context *ctx, int32_t which, int64_t index, int32_t *i
  * the context's stream. */
 int esc_light_list_read(esc_context *ctx, int32_t which, int32_t info[8], int32_t *face_counts,
                         int32_t *face_ids, int64_t first_cell, int64_t n_cells, int32_t *cell_ids);
+
+/* ... and the packed form of the sphere light lists (csrc/rt_device.h LightLists::pk_*), the form the
+ * shadow sweep reads.  info receives {lights with lists, R, slots per cell in `slots` (2 * list capacity),
+ * spheres per step (4), steps of all cells, 0, 0, 0}.  Either output may be NULL:
+ *   steps [n_cells]                     the cell's step count; -1: the cell is over its list capacity and
+ *                                       is not served (the sweep runs instead);
+ *   slots [n_cells][2 * list capacity]  the cell's 4 * steps slots in the order they are tested, each the
+ *                                       position 2 j + h of a sphere in the group-sorted table (half h of
+ *                                       pair record j) or -1 for a pad slot; -1 after them.
+ * Returns as esc_light_list_read does; 0 also when the valid lists have no packed form. */
+int esc_light_list_packed_read(esc_context *ctx, int32_t info[8], int64_t first_cell, int64_t n_cells,
+                               int32_t *steps, int32_t *slots);
 
 /* Host only, for inspection and tests: the spatial order the groups are cut from (k-d median
  * splits over the points; csrc/rt_device.h SphGroups / TriGroups).  xyz holds 3 floats per point;

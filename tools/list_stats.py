@@ -37,3 +37,17 @@ for which, name in ((0, "spheres"), (1, "triangles"), (2, "light-list cells (sph
         faces = c.reshape(-1, R, R)
         print("  per face (+x -x +y -y +z -z per light): mean", [round(float(f.mean()), 2) for f in faces],
               "max", [int(f.max()) for f in faces])
+    if which == 2:  # the packed form the shadow sweep reads (rt_lists.h k_pack_light_cells)
+        pk = r.light_lists_packed()
+        if pk is None:
+            print(cfg, "packed light-list cells: none")
+            continue
+        st = pk["steps"].reshape(-1)
+        kept = (pk["slots"] >= 0).sum(axis=-1).reshape(-1)
+        ne = c.reshape(-1) > 0
+        rec = np.minimum(c.reshape(-1), L["cap"])
+        print(cfg, "packed light-list cells:", pk["total_steps"], "steps of 4 spheres,",
+              round(pk["total_steps"] * 80 / 1e6, 2), "MB (records + positions)")
+        print("  per non-empty cell: records", float(rec[ne].mean()), "kept halves", float(kept[ne].mean()), "max", int(kept.max()),
+              "sphere slots tested by id lists (8 ceil(rec / 4))", float((8 * ((rec[ne] + 3) // 4)).mean()),
+              "packed (4 steps)", float((4 * st[ne]).mean()), "unserved cells", int((st < 0).sum()))
