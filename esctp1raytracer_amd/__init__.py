@@ -14,14 +14,14 @@ import numpy as np
 from . import _capi
 from ._capi import (ESC_FACE_FIXED, ESC_FACE_HASH, ESC_STAGE_AUTO, ESC_STAGE_BVH, ESC_STAGE_LDS,
                     ESC_RENDER_EXACT_ONLY, ESC_RENDER_INDEX_ORDER, ESC_RENDER_SHADE_FUSED,
-                    ESC_RENDER_SHADE_QUEUE, ESC_RENDER_TIME_KERNELS, ESC_RENDER_NO_TILE_LISTS, ESC_RENDER_NO_LIGHT_LISTS, ESC_RENDER_TWO_KERNELS, ESC_RENDER_BVH_HEURISTIC_PADS, ESC_RENDER_NO_COUNTERS, ESC_RENDER_NO_PACKED_LIGHT_LISTS,
+                    ESC_RENDER_SHADE_QUEUE, ESC_RENDER_TIME_KERNELS, ESC_RENDER_NO_TILE_LISTS, ESC_RENDER_NO_LIGHT_LISTS, ESC_RENDER_TWO_KERNELS, ESC_RENDER_BVH_HEURISTIC_PADS, ESC_RENDER_NO_COUNTERS, ESC_RENDER_NO_PACKED_LIGHT_LISTS, ESC_RENDER_VOTE,
                     ESC_STAGE_SMEM, ESC_TRANSMIT_OFF, ESC_TRANSMIT_REFRACT, ESC_TRANSMIT_FRESNEL, EscError,
                     check)
 
 __all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "live_device_allocations", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table", "environment_sky", "environment_lookup_host",
            "EscError", "ESC_FACE_FIXED", "ESC_FACE_HASH", "ESC_STAGE_AUTO", "ESC_STAGE_SMEM",
            "ESC_STAGE_LDS", "ESC_STAGE_BVH", "ESC_RENDER_EXACT_ONLY", "ESC_RENDER_TIME_KERNELS", "ESC_RENDER_INDEX_ORDER", "ESC_RENDER_SHADE_QUEUE",
-           "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "ESC_RENDER_NO_PACKED_LIGHT_LISTS", "ESC_TRANSMIT_OFF", "ESC_TRANSMIT_REFRACT", "ESC_TRANSMIT_FRESNEL", "version"]
+           "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "ESC_RENDER_NO_PACKED_LIGHT_LISTS", "ESC_RENDER_VOTE", "ESC_TRANSMIT_OFF", "ESC_TRANSMIT_REFRACT", "ESC_TRANSMIT_FRESNEL", "version"]
 
 
 def _f32(a, shape=None):
@@ -197,6 +197,12 @@ class Scene:
         out = np.zeros(check(self._lib.esc_scene_table(self._h, which, None, 0)), np.uint8)
         check(self._lib.esc_scene_table(self._h, which, out.ctypes.data, out.size))
         return out
+
+    def shadow_origins_inside(self, origin):
+        """Host only: esc_scene_shadow_origins_inside -- True when every shadow-ray origin of a camera at
+        `origin` provably lies in the scene's grown box."""
+        o = _f32(origin, (3,))
+        return bool(check(self._lib.esc_scene_shadow_origins_inside(self._h, _fp(o))))
 
     def flatten_ispc(self, sort_by_centroid_x=False):
         """flatten_scene_ispc (flatten_iscp.cpp:35-111) -> FlatScene."""
@@ -454,6 +460,18 @@ class Renderer:
         ms = np.zeros(2, np.float32)
         check(self._lib.esc_last_kernel_ms(self._h, _fp(ms)))
         return float(ms[0]), float(ms[1])
+
+    def last_frame_kernel(self):
+        """esc_last_frame_kernel: the ESC_FRAME_KERNEL_* bits of the one-kernel frame the last frame
+        launched (0: it took another path), as a dict of booleans."""
+        bits = check(self._lib.esc_last_frame_kernel(self._h))
+        return {"fused": bool(bits & _capi.ESC_FRAME_KERNEL_FUSED), "grp": bool(bits & _capi.ESC_FRAME_KERNEL_GRP),
+                "tgrp": bool(bits & _capi.ESC_FRAME_KERNEL_TGRP), "idl": bool(bits & _capi.ESC_FRAME_KERNEL_IDL),
+                "sure": bool(bits & _capi.ESC_FRAME_KERNEL_SURE)}
+
+    def frame_tripwire(self):
+        """esc_frame_tripwire: reads and clears the "unserved wave in a frame without fallback" word; 0."""
+        return check(self._lib.esc_frame_tripwire(self._h))
 
     def reset_counters(self):
         check(self._lib.esc_reset_counters(self._h))

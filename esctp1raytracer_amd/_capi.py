@@ -42,6 +42,12 @@ ESC_RENDER_TWO_KERNELS = 128
 ESC_RENDER_BVH_HEURISTIC_PADS = 256
 ESC_RENDER_NO_COUNTERS = 512
 ESC_RENDER_NO_PACKED_LIGHT_LISTS = 1024
+ESC_RENDER_VOTE = 2048
+ESC_FRAME_KERNEL_FUSED = 1
+ESC_FRAME_KERNEL_GRP = 2
+ESC_FRAME_KERNEL_TGRP = 4
+ESC_FRAME_KERNEL_IDL = 8
+ESC_FRAME_KERNEL_SURE = 16
 # ESC_TABLE_*: the index of a name is its value
 ESC_TABLE_NAMES = ("tri", "tri_n", "sph", "sph_mat", "mat", "transmit", "lights", "light_points",
                    "sph2", "sph2_f", "sph2_ord", "sph2_f_ord", "tri2_f", "tri2_pf",
@@ -244,6 +250,9 @@ SIGNATURES = {
                                 C.c_double]),
     "esc_group_order": (C.c_int, [_F, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I32]),
     "esc_last_kernel_ms": (C.c_int, [_P, _F]),
+    "esc_last_frame_kernel": (C.c_int, [_P]),
+    "esc_frame_tripwire": (C.c_int, [_P]),
+    "esc_scene_shadow_origins_inside": (C.c_int, [_P, _F]),
     "esc_reset_counters": (C.c_int, [_P]),
     "esc_read_counters": (C.c_int, [_P, C.POINTER(esc_counters)]),
     "esc_intersect_rays": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_uint32]),

@@ -50,7 +50,7 @@ extern "C" int esc_launch_bin_light(const esc::LightBins *g, const float *light_
                                     const esc::PrimBoxDev *sph_boxes, int n_sph,
                                     hipStream_t stream);
 extern "C" int esc_launch_render(const esc::RenderParams *p, int stage, int px,
-                                 hipStream_t stream, hipEvent_t between, int two_kernels);
+                                 hipStream_t stream, hipEvent_t between, int two_kernels, int *which);
 extern "C" int esc_launch_shade_queue(const esc::RenderParams *p, int li, int last, const int *segs,
                                       int n_segs, uint32_t *ctl, int n_wg, hipStream_t stream);
 extern "C" int esc_launch_primary_only(const esc::RenderParams *p, int px, hipStream_t stream);
@@ -152,6 +152,14 @@ struct esc_context {
   int32_t ll_pk_steps = -1;   // steps the packed cells of the valid lists use; < 0: not built for them
   int ll_face_mode = -1, ll_fixed_face = -1;
   bool ll_valid = false;
+  // no cell or face of the valid sphere lists is one the sweep refuses (light_list_refused, counted by
+  // k_pack_light_cells<false> and read back with the step total)
+  bool ll_complete = false;
+  // "every shadow origin of this camera lies in the grown box" (esc::shadow_origins_inside), per camera
+  // origin and scene; sure_epoch: the scene it was asked of
+  float sure_origin[3] = {0, 0, 0};
+  bool sure_inside = false, sure_known = false;
+  int last_frame_kernel = 0;     // ESC_FRAME_KERNEL_* bits of the last frame (esc_last_frame_kernel)
   std::vector<esc::DevLight> h_lights;
   // ESC_STAGE_BVH: host copy of the tables the builder reads, the tree in HBM
   std::vector<esc::DevTri> h_tri;
@@ -348,6 +356,8 @@ int commit(esc_context *ctx, const Staged &s) {
   ctx->lists_valid = false;
   ctx->list_ids_stale = true;
   ctx->ll_valid = false;
+  ctx->ll_complete = false;
+  ctx->sure_known = false;
   ctx->h_lights = s.lights;
   ctx->h_tri = s.tri;
   ctx->h_sph = s.sph;
@@ -1033,7 +1043,10 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
         }
         if ((rc = ctx->frame.alloc(ctx->lt.esc, (size_t)n_listed * esc::kLightEscCap))) return rc;
         if ((rc = ctx->frame.alloc(ctx->ll.pk_cell, cells))) return rc;
-        if (!ctx->ll.pk_total && (rc = ctx->frame.alloc(ctx->ll.pk_total, 1))) return rc;
+        if (!ctx->ll.pk_total) { // steps, refused cells, and k_frame's tripwire (rt_device.h): zero once
+          if ((rc = ctx->frame.alloc(ctx->ll.pk_total, 3))) return rc;
+          HIP_TRY(hipMemsetAsync(ctx->ll.pk_total, 0, 12, ctx->stream));
+        }
         ctx->ll_alloc_lights = n_listed;
         ctx->ll_valid = false;
       }
@@ -1065,15 +1078,17 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
         // the packed form of the sphere lists: count, size the stream exactly (one read-back per scene
         // and sample point; this path never runs inside a capture), fill
         ctx->ll_pk_steps = -1;
+        ctx->ll_complete = false;
         if (p.ll.enabled) {
-          HIP_TRY(hipMemsetAsync(p.ll.pk_total, 0, 4, ctx->stream));
+          HIP_TRY(hipMemsetAsync(p.ll.pk_total, 0, 8, ctx->stream));
           if ((e = esc_launch_light_pack(&p, 0, ctx->stream))) {
             set_error(std::string("k_pack_light_cells launch: ") + hipGetErrorString((hipError_t)e));
             return ESC_ERR_HIP;
           }
           HIP_TRY(hipStreamSynchronize(ctx->stream));
-          int32_t steps = 0;
-          HIP_TRY(hipMemcpy(&steps, p.ll.pk_total, 4, hipMemcpyDeviceToHost));
+          int32_t total[2] = {0, 0}; // steps; cells and faces the sweep would refuse
+          HIP_TRY(hipMemcpy(total, p.ll.pk_total, 8, hipMemcpyDeviceToHost));
+          const int32_t steps = total[0];
           if (steps < 0) {
             set_error("k_pack_light_cells: the packed light lists do not fit 2^31 steps");
             return ESC_ERR_HIP;
@@ -1095,6 +1110,7 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
             return ESC_ERR_HIP;
           }
           ctx->ll_pk_steps = steps;
+          ctx->ll_complete = total[1] == 0;
         }
         ctx->ll.n_listed = ctx->lt.n_listed = n_listed;
         ctx->ll.R = ctx->lt.R = Rr;
@@ -1172,6 +1188,7 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
   }
   const bool timed = (opts->flags & ESC_RENDER_TIME_KERNELS) != 0;
   ctx->ev_valid = false;
+  ctx->last_frame_kernel = 0;
   if (timed) {
     for (auto &ev : ctx->ev)
       if (!ev) HIP_TRY(hipEventCreate(&ev));
@@ -1210,8 +1227,29 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
       const char *v = std::getenv("ESC_FRAME");
       return v && std::strcmp(v, "2") == 0;
     }();
+    // k_frame without the vote and the fallback sweep (rt_kernels.hip "SURE"): only when no wave can
+    // be refused -- complete packed sphere lists, one light (quirk S3 starts a later light's ray
+    // wherever the previous light's t left it), and a camera whose primary hits all give shadow
+    // origins inside the box (asked once per camera origin and scene).  The launch code adds what it
+    // can see in p: every light covered, no triangle groups, the packed instantiation.
+    static const bool env_vote = [] {
+      const char *v = std::getenv("ESC_SURE");
+      return v && std::strcmp(v, "0") == 0;
+    }();
+    if (!env_vote && !(opts->flags & ESC_RENDER_VOTE) && p.shadows && p.ll.enabled && p.ll.pk_cell &&
+        ctx->ll_valid && ctx->ll_complete && ctx->n_lights == 1 && p.tg.n_grp == 0) {
+      if (!ctx->sure_known || std::memcmp(ctx->sure_origin, cam->origin, 12) != 0) {
+        ctx->sure_inside = esc::shadow_origins_inside(cam->origin, ctx->scene_lo, ctx->scene_hi, ctx->h_tri.data(),
+                                                      ctx->h_tri.size(), ctx->n_lights);
+        std::memcpy(ctx->sure_origin, cam->origin, 12);
+        ctx->sure_known = true;
+      }
+      p.sure = ctx->sure_inside ? 1 : 0;
+    }
+    int which = 0;
     e = esc_launch_render(&p, stage, px, ctx->stream, timed ? ctx->ev[1] : nullptr,
-                          (env_two || (opts->flags & ESC_RENDER_TWO_KERNELS)) ? 1 : 0);
+                          (env_two || (opts->flags & ESC_RENDER_TWO_KERNELS)) ? 1 : 0, &which);
+    ctx->last_frame_kernel = which;
   }
   if (timed && !e) {
     HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
@@ -1688,6 +1726,44 @@ int esc_last_kernel_ms(esc_context *ctx, float ms[2]) {
   HIP_TRY(hipEventElapsedTime(&ms[0], ctx->ev[0], ctx->ev[1]));
   HIP_TRY(hipEventElapsedTime(&ms[1], ctx->ev[1], ctx->ev[2]));
   return ESC_OK;
+}
+
+int esc_last_frame_kernel(esc_context *ctx) {
+  if (!ctx) {
+    set_error("esc_last_frame_kernel: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  return ctx->last_frame_kernel;
+}
+
+int esc_frame_tripwire(esc_context *ctx) {
+  if (!ctx) {
+    set_error("esc_frame_tripwire: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  if (!ctx->ll.pk_total) return 0; // no light lists yet: no frame without fallback can have run
+  HIP_TRY(hipSetDevice(ctx->device));
+  int32_t w = 0;
+  HIP_TRY(hipMemcpyAsync(&w, ctx->ll.pk_total + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipMemsetAsync(ctx->ll.pk_total + 2, 0, 4, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return w != 0 ? 1 : 0;
+}
+
+int esc_scene_shadow_origins_inside(const esc_scene *scene, const float origin[3]) {
+  if (!scene || !origin) {
+    set_error("esc_scene_shadow_origins_inside: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  Staged s;
+  int rc = stage_scene(*scene, s);
+  if (rc) return rc;
+  esc::SceneTables t;
+  esc::build_scene_tables(s, t);
+  return esc::shadow_origins_inside(origin, t.scene_lo, t.scene_hi, s.tri.data(), s.tri.size(),
+                                    (int)s.lights.size())
+             ? 1
+             : 0;
 }
 
 // ---- batched ray queries (rt_query.hip) ---------------------------------------------------

@@ -343,7 +343,9 @@ struct LightLists {
   LightCell *pk_cell;  // [cells]: where the cell's steps start and how many (n_steps < 0: over the cap)
   DevSphPair *pk_rec;  // [2 * steps + 2]: the steps of all cells, back to back; spare slots are pad halves
   int32_t *pk_pos;     // [4 * steps]: every slot's position 2 j + h in the sorted table (-1: pad)
-  int32_t *pk_total;   // [1]: steps handed out (k_pack_light_cells<false>)
+  int32_t *pk_total;   // [3]: steps handed out; cells the sweep would refuse (k_pack_light_cells<false>,
+                       // light_list_refused); and the tripwire: k_frame<..., SURE> writes 1 there when
+                       // shadow_wave_lists reports an unserved wave after all (esc_frame_tripwire)
 };
 
 // hand-over between k_primary and k_shade: the closest hit of every pixel of the band
@@ -518,7 +520,11 @@ struct RenderParams {
   const DevMat *mat;      // [n_geom + n_sphere_materials]
   const DevLight *lights;
   const float *light_points; // xyz0 per candidate point
-  int32_t shadows, face_mode, fixed_face, pad0;
+  int32_t shadows, face_mode, fixed_face;
+  // 1: the host has proved that shadow_wave_lists serves every wave of this frame (complete light
+  // lists, every shadow origin inside [scene_lo, scene_hi]: DESIGN.md 3.9 "Frames that need no
+  // fallback") -- the launch may take k_frame's SURE instantiation
+  int32_t sure;
   uint64_t seed;
   float *out_f32;   // band-local, may be null
   uint8_t *out_u8;  // band-local, may be null

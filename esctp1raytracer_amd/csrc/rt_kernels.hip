@@ -36,6 +36,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "rt_device.h"
 #include "rt_math.h"
@@ -949,7 +950,8 @@ DEVINL bool wg_vote_any(int *word, int &k, bool mine) {
 // anyhit_tri call the segment loop makes) or has light lists for this light.  The calls, the
 // bookkeeping of `Any` between the kinds (triangles first; a ray a triangle stopped does not look
 // at the spheres) and the counter flags are those of shadow_sweep_smem, statement for statement.
-template <bool TGRP> DEVINL bool shadow_lists_cover(const RenderParams &p, int li) {
+// (__host__ too: the launch code asks the same question of every light before it takes k_frame's SURE form)
+template <bool TGRP> __host__ DEVINL bool shadow_lists_cover(const RenderParams &p, int li) {
   if (!p.use_filter) return false;
   bool tri_ok = p.n_tri == 0 || p.n_tri < 8;
   if (TGRP && p.tg.n_grp > 0)
@@ -1348,14 +1350,25 @@ DEVINL void emit_counters_n(const RenderParams &p, int tid, int lane, uint32_t n
     atomicAdd(&p.counters[(blockIdx.x % kCounterSets) * 8 + tid], wg_cnt[tid]);
 }
 
-template <bool GRP, bool TGRP, bool IDL = false>
-__global__ void __launch_bounds__(256, TGRP ? 4 : 5) k_frame(const RenderParams p) {
-  __shared__ RepackLds lds_rays;
+// SURE (RenderParams::sure, DESIGN.md 3.9 "Frames that need no fallback"): the host has proved that
+// shadow_wave_lists serves every wave of this frame -- the light lists are complete and every shadow
+// origin lies in the box they were built for.  Then no wave has anything to tell the others: the
+// instantiation has no vote (a barrier and an LDS word per light and pixel), no shadow_sweep_smem and
+// no RepackLds, and the registers, the SGPR spills and the 19 KB of LDS they cost the served path go
+// with them.  The arithmetic of every ray is the same statements.  A `false` from shadow_wave_lists is
+// unreachable; should it happen all the same, lane 0 leaves 1 in the tripwire word and the wave goes on as served.
+struct NoLds {};
+#ifndef ESC_FRAME_SURE_WAVES
+#define ESC_FRAME_SURE_WAVES 6
+#endif
+template <bool GRP, bool TGRP, bool IDL = false, bool SURE = false>
+__global__ void __launch_bounds__(256, TGRP ? 4 : (SURE ? ESC_FRAME_SURE_WAVES : 5)) k_frame(const RenderParams p) {
+  __shared__ typename std::conditional<SURE, NoLds, RepackLds>::type lds_rays;
   __shared__ float park[2][6][256]; // per pixel q of thread t: dir xyz, t, v, idx
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[16];
-  __shared__ int vote_word[4];
+  __shared__ int vote_word[SURE ? 1 : 4];
   int vote_k = 0;
-  wg_vote_init(vote_word);
+  if constexpr (!SURE) wg_vote_init(vote_word);
   const int tid = threadIdx.x;
   { // ---- camera.h:31-34 + main.cpp:722: both pixels of every lane (k_primary's body)
     const Tile<2> T(p, Tile<2>::Grid2D{});
@@ -1461,7 +1474,14 @@ __global__ void __launch_bounds__(256, TGRP ? 4 : 5) k_frame(const RenderParams 
           int go = 0, sw = 0;
           bool tg = false, sgp = false;
           const bool ok = shadow_wave_lists<TGRP, IDL>(p, li, ro, rL, af, go, tg, sgp, sw);
-          if (!wg_vote_any(vote_word, vote_k, !ok)) { // every wave of the workgroup was served
+          bool all_ok;
+          if constexpr (SURE) {
+            if (!ok && lane == 0) p.ll.pk_total[2] = 1; // unreachable (see above): seen by esc_frame_tripwire
+            all_ok = true;
+          } else {
+            all_ok = !wg_vote_any(vote_word, vote_k, !ok);
+          }
+          if (all_ok) { // every wave of the workgroup was served
             a[0].kocc = af.kocc;
             a[0].tocc = af.tocc;
             grp_open = go;
@@ -1471,9 +1491,11 @@ __global__ void __launch_bounds__(256, TGRP ? 4 : 5) k_frame(const RenderParams 
             served = true;
           }
         }
-        if (!served)
-          shadow_sweep_smem<TGRP, IDL>(p, lds_rays, tid, wave, lane, li, ro, rL, a, N, r, g, b, t, mi, grp_open,
-                                  tri_groups, sph_groups, n_swept);
+        if constexpr (!SURE) {
+          if (!served)
+            shadow_sweep_smem<TGRP, IDL>(p, lds_rays, tid, wave, lane, li, ro, rL, a, N, r, g, b, t, mi, grp_open,
+                                    tri_groups, sph_groups, n_swept);
+        }
       }
       if (has_hit) {
         if (p.shadows && p.counters) { // (instrumentation: ESC_RENDER_NO_COUNTERS skips it)
@@ -1993,8 +2015,10 @@ extern "C" int esc_launch_primary_only(const esc::RenderParams *p, int px, hipSt
 
 // stage: 1 SMEM (always 2 px), 2 LDS, 3 BVH (px ignored).  px: pixels per work-item of the LDS primary pass (1, 2 or 4); the shade
 // pass always carries one pixel per work-item.
+// *which: the k_frame instantiation launched, as ESC_FRAME_KERNEL_* bits (0: another path)
 extern "C" int esc_launch_render(const esc::RenderParams *p, int stage, int px, hipStream_t stream,
-                                 hipEvent_t between, int two_kernels) {
+                                 hipEvent_t between, int two_kernels, int *which) {
+  *which = 0;
   if (p->n_local_rows <= 0 || p->W <= 0) return 0;
   using esc::v2f;
   const int tiles_y = (p->n_local_rows + esc::kTileH - 1) / esc::kTileH;
@@ -2018,12 +2042,20 @@ extern "C" int esc_launch_render(const esc::RenderParams *p, int stage, int px, 
     const dim3 grid((unsigned)((p->W + 63) / 64), (unsigned)tiles_y); // (x, y) = the tile: Tile<2>::Grid2D
     const bool grp = p->use_filter && (p->sg.n_grp > 0 || p->tg.n_grp > 0);
     const bool tgrp = p->use_filter && p->tg.n_grp > 0;
+    // SURE: the host's proof (p->sure) covers rays that the sphere lists and the direct triangle loop
+    // serve, so every light must be one shadow_lists_cover accepts -- the kernel then never looks for
+    // its fallback.  Scenes with triangle groups keep the vote (their lists have no completeness word).
+    bool sure = p->sure && p->ll.pk_total && p->shadows && grp && !tgrp && !idl && p->n_lights > 0;
+    for (int li = 0; sure && li < p->n_lights; ++li) sure = esc::shadow_lists_cover<false>(*p, li);
+    *which = 1 | (grp ? 2 : 0) | (tgrp ? 4 : 0) | (idl || !grp ? 8 : 0) | (sure ? 16 : 0);
     if (tgrp && idl)
       hipLaunchKernelGGL((esc::k_frame<true, true, true>), grid, dim3(256), 0, stream, *p);
     else if (tgrp)
       hipLaunchKernelGGL((esc::k_frame<true, true>), grid, dim3(256), 0, stream, *p);
     else if (grp && idl)
       hipLaunchKernelGGL((esc::k_frame<true, false, true>), grid, dim3(256), 0, stream, *p);
+    else if (sure)
+      hipLaunchKernelGGL((esc::k_frame<true, false, false, true>), grid, dim3(256), 0, stream, *p);
     else if (grp)
       hipLaunchKernelGGL((esc::k_frame<true, false>), grid, dim3(256), 0, stream, *p);
     else // (no groups: no light lists)

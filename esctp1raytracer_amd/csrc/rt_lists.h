@@ -730,12 +730,25 @@ template <bool TRI> __global__ void __launch_bounds__(256) k_sort_light_cells(co
 // position for the accept branch.  One thread per cell, twice: FILL = false counts the kept halves
 // and takes the cell's steps from a bump counter (so a cell's OFFSET depends on the order the atomics
 // ran in; its contents do not), the host reads the total and sizes pk_rec / pk_pos, FILL = true writes.
+//
+// When the sweep (anyhit_sph_light_lists) refuses a cell: its face's own list or the cell itself is
+// over its cap, or the face's lists are off.  n: the cell's count, or the steps of its packed form
+// (-1 when the count is over the cap).  The count pass below asks the same question of every cell
+// once per build and leaves the number of refused cells in pk_total[1]: zero means no ray that
+// starts inside the box can be refused (RenderParams::sure).
+template <typename Hdr> DEVINL bool light_list_refused(int n_glob, int n, Hdr hdr) {
+  return n_glob > kTileGlobalCap || n > kLightListCap || n < 0 || hdr[2] != 0;
+}
 template <bool FILL> __global__ void __launch_bounds__(256) k_pack_light_cells(const RenderParams p) {
   const LightLists LL = p.ll;
   const int Rr = LL.R, cells_per_light = 6 * Rr * Rr;
   const int cell = blockIdx.x * 256 + (int)threadIdx.x;
   if (cell >= LL.n_listed * cells_per_light) return;
   const int n = LL.cnt[cell];
+  if (!FILL) { // (a refused face counts once per cell: only "none" is read)
+    const int32_t *hdr = LL.hdr + (size_t)(cell / (Rr * Rr)) * kTileHdrInts;
+    if (light_list_refused(hdr[0], n, hdr)) atomicAdd(LL.pk_total + 1, 1);
+  }
   if (n <= 0 || n > kLightListCap) {
     if (!FILL) LL.pk_cell[cell] = LightCell{0, n > 0 ? -1 : 0};
     return;
@@ -887,7 +900,7 @@ DEVINL bool anyhit_sph_light_lists(const LightLists &LL, int cell, FetchE rece, 
     const int n_glob = hdr[0];
     const int ce0 = packed ? ((ListPtr)(uintptr_t)LL.pk_cell)[2 * c] : 0;
     const int n = packed ? ((ListPtr)(uintptr_t)LL.pk_cell)[2 * c + 1] : cnt[c];
-    if (n_glob > kTileGlobalCap || n > kLightListCap || n < 0 || hdr[2] != 0) return false;
+    if (light_list_refused(n_glob, n, hdr)) return false;
     const SmemFetch<DevIdx4> glob{reinterpret_cast<const DevIdx4 *>(LL.hdr + (size_t)(c / cells_per_face) * kTileHdrInts + 8)};
     auto batch = [&](const DevIdx4 &I) { // four pair records = 8 spheres
       n_tests += (a.tb > 0.f) ? 8 : 0;

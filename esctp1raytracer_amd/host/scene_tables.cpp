@@ -563,4 +563,51 @@ void build_scene_tables(const Staged &s, SceneTables &t) {
                                  : std::min(t.min_light_faces, (int)s.lights[i].n_faces);
 }
 
+// DESIGN.md 3.9 "Frames that need no fallback", statement (I): the names below are the proof's.
+// Everything in double; each comparison leans to "no".
+bool shadow_origins_inside(const float origin[3], const float lo[3], const float hi[3], const DevTri *tri,
+                           size_t n_tri, int n_lights) {
+  if (n_lights != 1) return false; // quirk S3: a later light's ray starts wherever the previous t left it
+  double S = 0.0, A = 0.0, M2 = 0.0, oinf = 0.0;
+  for (int a = 0; a < 3; a++) {
+    if (!std::isfinite(origin[a]) || !std::isfinite(lo[a]) || !std::isfinite(hi[a]) || !(lo[a] <= hi[a]))
+      return false;
+    S += (double)hi[a] - (double)lo[a];
+    A = std::max(A, std::max(std::fabs((double)lo[a]), std::fabs((double)hi[a])));
+    const double far = std::max(std::fabs((double)origin[a] - lo[a]), std::fabs((double)origin[a] - hi[a]));
+    M2 += far * far;
+    oinf = std::max(oinf, std::fabs((double)origin[a]));
+  }
+  const double M = std::sqrt(M2);            // the camera's distance from the farthest corner of the box
+  const double m = S / 26.0 - 0x1p-22 * A;   // the margin: 0.05 of the ungrown extents' sum, S = 1.3 of it
+  if (!(m > 0.0) || !std::isfinite(M)) return false;
+  const double e_fp = 0x1p-20 * (1.0 + M + m + oinf); // fl(origin + dir (t - eps)), the tails' casts
+  const double e_sph = 0x1p-8 * M;                    // a sphere's root: sqrt(66 u) max(|w|, r) + 4u ...
+  double e_tri = 0.0;
+  const double cu = 0x1p-20; // 16 u: what a numerator or det is off by, over the product of its lengths
+  for (size_t i = 0; i < n_tri; i++) {
+    const DevTri &T = tri[i];
+    double e1[3], e2[3], w[3], n[3];
+    for (int a = 0; a < 3; a++) {
+      e1[a] = T.e1[a];
+      e2[a] = T.e2[a];
+      w[a] = (double)origin[a] - (double)T.v0[a];
+    }
+    n[0] = e1[1] * e2[2] - e1[2] * e2[1];
+    n[1] = e1[2] * e2[0] - e1[0] * e2[2];
+    n[2] = e1[0] * e2[1] - e1[1] * e2[0];
+    const double L1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+    const double L2 = std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+    if (L1 == 0.0 && L2 == 0.0) continue; // a pad: det is exactly 0, never accepted
+    const double A2 = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    const double W = 1.0001 * std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+    const double hA2 = std::fabs(w[0] * n[0] + w[1] * n[1] + w[2] * n[2]); // h A2 = |w . (e1 x e2)|
+    const double Q = cu * W * L1 * L2;
+    const double Dmin = std::min(0.5 * A2 - cu * L1 * L2, (0.86 * hA2 - 3.0 * Q) / (1.0001 * (L1 + L2 + W)));
+    if (!(Dmin > 0.0)) return false; // a sliver, or the camera (nearly) in the triangle's plane
+    e_tri = std::max(e_tri, 4.01 * Q / Dmin);
+  }
+  return e_fp + std::max(e_sph, e_tri) <= m;
+}
+
 } // namespace esc

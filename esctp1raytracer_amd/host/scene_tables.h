@@ -60,4 +60,12 @@ struct SceneTables {
 
 void build_scene_tables(const Staged &s, SceneTables &t);
 
+// A sufficient condition (DESIGN.md 3.9 "Frames that need no fallback") for: every shadow-ray origin
+// fl(origin + dir (t - eps)) of a camera at `origin`, over every unit direction and every primary hit the
+// kernels accept, lies in [lo, hi] = SceneTables::scene_lo / scene_hi.  It looks at the camera's distance
+// from the box, the box's size and the camera's height over each triangle's plane.  false: not proved
+// (too far away, nearly in a triangle's plane, more than one light, something not finite).
+bool shadow_origins_inside(const float origin[3], const float lo[3], const float hi[3], const DevTri *tri,
+                           size_t n_tri, int n_lights);
+
 } // namespace esc

@@ -314,7 +314,23 @@ enum {
    * 3.9).  This flag makes it sweep the lists of pair-record ids instead, as before the packed form
    * existed -- the same image bit for bit, more tests: the A/B switch, and what the tests compare
    * against.  The lists themselves (esc_light_list_read) are the same either way. */
-  ESC_RENDER_NO_PACKED_LIGHT_LISTS = 1024
+  ESC_RENDER_NO_PACKED_LIGHT_LISTS = 1024,
+  /* When the host can prove that the light lists serve every shadow ray of a frame -- no cell or face
+   * list over its cap, one light, a camera close enough to the scene that every shadow origin lies in
+   * the box the lists were built for -- the one-kernel frame runs an instantiation
+   * without the per-light workgroup vote and without the fallback sweep behind it.  This flag (or
+   * $ESC_SURE=0) keeps the vote: the kernel every other frame runs anyway.  Same arithmetic, same
+   * image; the A/B switch.  esc_last_frame_kernel tells which one ran. */
+  ESC_RENDER_VOTE = 2048
+};
+
+/* esc_last_frame_kernel: the instantiation of the one-kernel frame (k_frame) the last frame launched */
+enum {
+  ESC_FRAME_KERNEL_FUSED = 1,  /* k_frame ran at all (0: two kernels, the queue form, another stage) */
+  ESC_FRAME_KERNEL_GRP = 2,    /* primary rays through the groups / tile lists */
+  ESC_FRAME_KERNEL_TGRP = 4,   /* the scene has triangle groups */
+  ESC_FRAME_KERNEL_IDL = 8,    /* sphere light lists read by ids (or not at all), not in packed form */
+  ESC_FRAME_KERNEL_SURE = 16   /* no vote, no fallback sweep (see ESC_RENDER_VOTE) */
 };
 
 typedef struct {
@@ -572,6 +588,19 @@ int esc_group_order(const float *xyz, int32_t count, int32_t run, int32_t big, i
 /* ms[0] = k_primary, ms[1] = k_shade of the last frame rendered with ESC_RENDER_TIME_KERNELS
  * (waits for that frame).  This is how bench.py prices each kernel against its own roof. */
 int esc_last_kernel_ms(esc_context *ctx, float ms[2]);
+/* ESC_FRAME_KERNEL_* bits of the last frame this context launched (esc_render_rows / esc_render_strips /
+ * esc_frame_record; a recorded frame keeps the kernel it was recorded with), or a negative error. */
+int esc_last_frame_kernel(esc_context *ctx);
+/* Reads and clears the word k_frame's ESC_FRAME_KERNEL_SURE instantiation sets when a wavefront was
+ * refused by the light lists after all -- which the launch conditions rule out: a check for tests, 0
+ * always.  Returns 0 or 1, or a negative error.  Synchronises the context's stream. */
+int esc_frame_tripwire(esc_context *ctx);
+/* Host only: 1 when every shadow-ray origin fl(origin + dir (t - eps)) of a camera at `origin` -- any
+ * direction, any primary hit the kernels accept in `scene` -- lies inside the scene's grown box
+ * (esc_scene_table_header scene_lo / scene_hi), by the sufficient condition of DESIGN.md 3.9; 0 when the
+ * condition does not hold (a camera too far away, or nearly in the plane of a triangle, a scene with more
+ * than one light, a non-finite coordinate); a negative error. */
+int esc_scene_shadow_origins_inside(const esc_scene *scene, const float origin[3]);
 int esc_reset_counters(esc_context *ctx);
 int esc_read_counters(esc_context *ctx, esc_counters *out);
 

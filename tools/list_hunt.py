@@ -1,5 +1,7 @@
 """Developer hunt: random scenes (tests/random_scenes.py), the default frame (tile lists + light lists) against
-the three-level group sweep (lists off) and, every fourth scene, the index-order sweep -- bit for bit.
+the three-level group sweep (lists off) and, every fourth scene, the index-order sweep -- bit for bit.  A frame
+that ran without the vote and the fallback sweep (k_frame's SURE form) is also compared with ESC_RENDER_VOTE, and
+its tripwire must read 0.
 python tools/list_hunt.py [n_scenes] [first_seed] [oracle_every]  (oracle_every k > 0: every k-th scene is
 also rendered by the CPU oracle and compared bit for bit)"""
 import os
@@ -20,15 +22,21 @@ oracle_every = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 checked = 0
 r = esc.Renderer(0)
 off = esc.ESC_RENDER_NO_TILE_LISTS | esc.ESC_RENDER_NO_LIGHT_LISTS
-bad = lit = listed = served = cones = 0
+bad = lit = listed = served = cones = sure = 0
 for seed in range(first, first + n):
     d, eye, look, W, H, vfov = random_scene(seed)
     r.upload(ol.scene_to_product(d))
     cam = esc.Camera.for_image(eye, look, W, H, vfov=vfov)
     a = r.render(cam, W, H)
+    was_sure = r.last_frame_kernel()["sure"]
+    tripped = r.frame_tripwire()
     st = [r.tile_lists(w) for w in range(4)]
     b = r.render(cam, W, H, flags=off)
     nd = int((a.view(np.uint32) != b.view(np.uint32)).any(axis=2).sum())
+    if was_sure:
+        sure += 1
+        v = r.render(cam, W, H, flags=esc.ESC_RENDER_VOTE)
+        nd += int((a.view(np.uint32) != v.view(np.uint32)).any(axis=2).sum()) + (W * H if tripped else 0)
     if seed % 4 == 0:
         c = r.render(cam, W, H, flags=esc.ESC_RENDER_INDEX_ORDER)
         nd += int((a.view(np.uint32) != c.view(np.uint32)).any(axis=2).sum())
@@ -46,4 +54,4 @@ for seed in range(first, first + n):
     if (seed - first) % 100 == 99:
         print(f"... {seed - first + 1} scenes, {bad} differ", flush=True)
 print(f"{n} scenes from seed {first}: {lit} with lit pixels, {listed} with tile lists, {served} with light lists, "
-      f"{cones} with escape entries, {checked} also against the oracle, {bad} with a difference")
+      f"{cones} with escape entries, {sure} without the vote, {checked} also against the oracle, {bad} with a difference")
