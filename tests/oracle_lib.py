@@ -377,11 +377,11 @@ def oracle_render(d, lookfrom, lookat, W, H, *, shadows=True, face_mode=ORC_FACE
     return img
 
 
-def oracle_shadow_rays(d, lookfrom, lookat, W, H, *, fixed_face=0):
+def oracle_shadow_rays(d, lookfrom, lookat, W, H, *, fixed_face=0, vfov=60.0):
     """orc_shadow_ray_record: (H * W, n_lights, 8) fp32 -- per pixel h * W + w and light {hitp, L, the ray's
     initial t, 0 no ray / 1 not occluded / 2 occluded}, as scan_row traced them (ORC_FACE_FIXED, every quirk)"""
     osc = d if isinstance(d, OracleScene) else OracleScene(d)
-    cam = oracle_camera(lookfrom, lookat, W, H)
+    cam = oracle_camera(lookfrom, lookat, W, H, vfov=vfov)
     o = orc_options(1, ORC_FACE_FIXED, fixed_face, 0, ORC_QUIRK_ALL)
     rec = np.zeros((H * W, max(osc.c.n_lights, 1), 8), np.float32)
     oracle().orc_shadow_ray_record(C.byref(osc.c), C.byref(cam), W, H, C.byref(o), fp(rec))
