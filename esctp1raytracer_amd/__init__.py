@@ -473,6 +473,14 @@ class Renderer:
         """esc_frame_tripwire: reads and clears the "unserved wave in a frame without fallback" word; 0."""
         return check(self._lib.esc_frame_tripwire(self._h))
 
+    def check_inv_det_exact(self, first_bits, n):
+        """esc_check_inv_det_exact over the float bit patterns first_bits .. first_bits + n - 1:
+        (patterns whose refined reciprocal differs from 1.0 / (double)x, the smallest of them)."""
+        bad, first = C.c_uint64(0), C.c_uint32(0)
+        check(self._lib.esc_check_inv_det_exact(self._h, int(first_bits) & 0xffffffff, int(n), C.byref(bad),
+                                                C.byref(first)))
+        return int(bad.value), int(first.value)
+
     def reset_counters(self):
         check(self._lib.esc_reset_counters(self._h))
 

@@ -252,6 +252,8 @@ SIGNATURES = {
     "esc_last_kernel_ms": (C.c_int, [_P, _F]),
     "esc_last_frame_kernel": (C.c_int, [_P]),
     "esc_frame_tripwire": (C.c_int, [_P]),
+    "esc_check_inv_det_exact": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint32)]),
     "esc_scene_shadow_origins_inside": (C.c_int, [_P, _F]),
     "esc_reset_counters": (C.c_int, [_P]),
     "esc_read_counters": (C.c_int, [_P, C.POINTER(esc_counters)]),

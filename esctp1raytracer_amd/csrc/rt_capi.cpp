@@ -49,7 +49,10 @@ extern "C" int esc_launch_bin_light(const esc::LightBins *g, const float *light_
                                     const esc::PrimBoxDev *tri_boxes, int n_tri,
                                     const esc::PrimBoxDev *sph_boxes, int n_sph,
                                     hipStream_t stream);
-extern "C" int esc_launch_render(const esc::RenderParams *p, int stage, int px,
+extern "C" int esc_launch_ray_tables(const esc::RenderParams *p, esc::RayEntry *col, esc::RayEntry *row,
+                                     hipStream_t stream);
+extern "C" int esc_launch_check_inv_det(uint32_t first, uint64_t n, unsigned long long *out, hipStream_t stream);
+extern "C" int esc_launch_render(const esc::RenderParams *p, const esc::RayTables *rays, int stage, int px,
                                  hipStream_t stream, hipEvent_t between, int two_kernels, int *which);
 extern "C" int esc_launch_shade_queue(const esc::RenderParams *p, int li, int last, const int *segs,
                                       int n_segs, uint32_t *ctl, int n_wg, hipStream_t stream);
@@ -134,6 +137,14 @@ struct esc_context {
   esc::DevMem call{this};
   bool prepared = false;
   float prepared_origin[3] = {0, 0, 0};
+  // k_frame's ray tables (rt_device.h RayTables): W and H entries, valid for ray_key; grow-only
+  esc::RayEntry *d_ray_col = nullptr, *d_ray_row = nullptr;
+  size_t ray_col_cap = 0, ray_row_cap = 0;
+  struct RayKey {
+    float cam[9]; // lower_left_corner, horizontal, vertical (the origin is subtracted per pixel)
+    int32_t W, H;
+  } ray_key{};
+  bool rays_valid = false;
   int32_t *d_hits = nullptr; // k_primary -> k_shade hand-over: 3 planes (idx, t, v) of hits_cap / 3 dwords
   size_t hits_cap = 0;
   // tile lists of the primary pass (rt_device.h TileLists), valid for list_key
@@ -942,6 +953,32 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
     ctx->prepared = true;
     ctx->epoch++;
   }
+  // ---- k_frame's ray tables (rt_device.h RayTables): per camera frame and image size, whatever path
+  // this call takes -- every frame k_frame renders finds them.  Rebuilt like the tables above: on this
+  // stream, behind the frames that read the old entries, and ending the recorded frames.
+  {
+    esc_context::RayKey key;
+    std::memset(&key, 0, sizeof(key));
+    std::memcpy(key.cam, cam->lower_left_corner, 12);
+    std::memcpy(key.cam + 3, cam->horizontal, 12);
+    std::memcpy(key.cam + 6, cam->vertical, 12);
+    key.W = W;
+    key.H = H;
+    if (!ctx->rays_valid || std::memcmp(&key, &ctx->ray_key, sizeof(key)) != 0) {
+      ctx->rays_valid = false;
+      int rc;
+      if ((rc = ctx->frame.grow(ctx->d_ray_col, ctx->ray_col_cap, (size_t)W))) return rc;
+      if ((rc = ctx->frame.grow(ctx->d_ray_row, ctx->ray_row_cap, (size_t)H))) return rc;
+      int e = esc_launch_ray_tables(&p, ctx->d_ray_col, ctx->d_ray_row, ctx->stream);
+      if (e) {
+        set_error(std::string("k_prepare_ray_tables launch: ") + hipGetErrorString((hipError_t)e));
+        return ESC_ERR_HIP;
+      }
+      ctx->ray_key = key;
+      ctx->rays_valid = true;
+      ctx->epoch++;
+    }
+  }
   // ---- tile lists of the primary pass (rt_lists.h): per camera and band, cached while both stand
   {
     static const bool env_nolists = [] {
@@ -1247,7 +1284,8 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
       p.sure = ctx->sure_inside ? 1 : 0;
     }
     int which = 0;
-    e = esc_launch_render(&p, stage, px, ctx->stream, timed ? ctx->ev[1] : nullptr,
+    const esc::RayTables rays{ctx->d_ray_col, ctx->d_ray_row};
+    e = esc_launch_render(&p, &rays, stage, px, ctx->stream, timed ? ctx->ev[1] : nullptr,
                           (env_two || (opts->flags & ESC_RENDER_TWO_KERNELS)) ? 1 : 0, &which);
     ctx->last_frame_kernel = which;
   }
@@ -1748,6 +1786,31 @@ int esc_frame_tripwire(esc_context *ctx) {
   HIP_TRY(hipMemsetAsync(ctx->ll.pk_total + 2, 0, 4, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return w != 0 ? 1 : 0;
+}
+
+int esc_check_inv_det_exact(esc_context *ctx, uint32_t first_bits, uint64_t n, uint64_t *mismatches,
+                            uint32_t *first_mismatch) {
+  if (!ctx || !mismatches || !first_mismatch || n > (1ull << 32)) {
+    set_error("esc_check_inv_det_exact: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  unsigned long long *d_out = nullptr, h_out[2] = {0ull, ~0ull};
+  int rc = ctx->call.alloc(d_out, 2);
+  if (rc) return rc;
+  hipError_t e = hipMemcpyAsync(d_out, h_out, sizeof(h_out), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = (hipError_t)esc_launch_check_inv_det(first_bits, n, d_out, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, sizeof(h_out), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  rc = ctx->call.release(d_out);
+  if (e != hipSuccess) {
+    set_error(std::string("esc_check_inv_det_exact: ") + hipGetErrorString(e));
+    return ESC_ERR_HIP;
+  }
+  if (rc) return rc;
+  *mismatches = h_out[0];
+  *first_mismatch = h_out[0] ? (uint32_t)h_out[1] : 0u;
+  return ESC_OK;
 }
 
 int esc_scene_shadow_origins_inside(const esc_scene *scene, const float origin[3]) {

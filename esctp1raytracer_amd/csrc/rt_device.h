@@ -542,6 +542,20 @@ struct RenderParams {
   LightBins lbins;              // ESC_STAGE_BVH only; n_points == 0: none
 };
 
+// Ray tables of k_frame ("Ray tables"): what camera.h:31-34 computes per pixel but that
+// depends on the pixel's column or row alone.  col[w] = llc + horizontal * (w / (W - 1)), W entries;
+// row[h] = vertical * (h / (H - 1)), H entries; each an f3 padded to 16 bytes.  Filled by
+// k_prepare_ray_tables with primary_dir's own statements; valid for one (llc, horizontal, vertical, W, H).
+// k_frame's own second argument, not a member of RenderParams: no other kernel's parameter block, and so
+// no other kernel's code, changes with it.
+struct alignas(16) RayEntry {
+  float x, y, z, pad;
+};
+struct RayTables {
+  const RayEntry *col;
+  const RayEntry *row;
+};
+
 // pixel tile of one 256-thread workgroup: 2 x 2 waves, each wave (16*PX) x 4 pixels, so the
 // tile is (32*PX) x 8 with PX = pixels per lane
 constexpr int kTileH = 8;

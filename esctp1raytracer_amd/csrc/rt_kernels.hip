@@ -558,11 +558,40 @@ DEVINL void write_tile(const RenderParams &p, const Tile<1> &T, int tid, float r
 }
 
 // main.cpp:709-713 + camera.h:31-34
+// The two terms that depend on the column or the row alone are functions of their own: primary_dir
+// computes them per pixel, k_prepare_ray_tables once per column and row for k_frame (rt_device.h
+// RayTables) -- the same statements under the same flags, so the same bits.
+DEVINL f3 ray_col(const RenderParams &p, int w) {
+  const float is = (float)w / (float)(p.W - 1);
+  return ld3(p.llc) + ld3(p.horizontal) * is;
+}
+DEVINL f3 ray_row(const RenderParams &p, int h) {
+  const float it = (float)h / (float)(p.H - 1);
+  return ld3(p.vertical) * it;
+}
 DEVINL f3 primary_dir(const RenderParams &p, int w, int h) {
   const f3 origin = mk(p.origin[0], p.origin[1], p.origin[2]);
-  const float is = (float)w / (float)(p.W - 1);
-  const float it = (float)h / (float)(p.H - 1);
-  return normalize(((ld3(p.llc) + ld3(p.horizontal) * is) + ld3(p.vertical) * it) - origin);
+  return normalize((ray_col(p, w) + ray_row(p, h)) - origin);
+}
+// ... and k_frame's form of it.  The tables hold W and H entries and the indices are clamped to them:
+// a lane of an edge tile, or of the rows below a short last strip, forms w >= W or h >= H (never a
+// negative one: w0, lx0, h0, ly >= 0), reads the last entry instead, and neither stores nor counts
+// what it traces (`inside` is false for it).  So no read leaves the tables whatever the strips are.
+DEVINL f3 primary_dir(const RenderParams &p, const RayTables &rt, int w, int h) {
+  const f3 origin = mk(p.origin[0], p.origin[1], p.origin[2]);
+  const RayEntry c = rt.col[min(w, p.W - 1)], r = rt.row[min(h, p.H - 1)];
+  return normalize((mk(c.x, c.y, c.z) + mk(r.x, r.y, r.z)) - origin);
+}
+__global__ void __launch_bounds__(256) k_prepare_ray_tables(const RenderParams p, RayEntry *col, RayEntry *row) {
+  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (i < p.W) {
+    const f3 c = ray_col(p, i);
+    col[i] = RayEntry{c.x, c.y, c.z, 0.f};
+  }
+  if (i < p.H) {
+    const f3 r = ray_row(p, i);
+    row[i] = RayEntry{r.x, r.y, r.z, 0.f};
+  }
 }
 
 // This thread's tile position, RECOMPUTED from the thread id through an opaque copy: used by
@@ -1362,7 +1391,8 @@ struct NoLds {};
 #define ESC_FRAME_SURE_WAVES 6
 #endif
 template <bool GRP, bool TGRP, bool IDL = false, bool SURE = false>
-__global__ void __launch_bounds__(256, TGRP ? 4 : (SURE ? ESC_FRAME_SURE_WAVES : 5)) k_frame(const RenderParams p) {
+__global__ void __launch_bounds__(256, TGRP ? 4 : (SURE ? ESC_FRAME_SURE_WAVES : 5)) k_frame(const RenderParams p,
+                                                                                             const RayTables rays) {
   __shared__ typename std::conditional<SURE, NoLds, RepackLds>::type lds_rays;
   __shared__ float park[2][6][256]; // per pixel q of thread t: dir xyz, t, v, idx
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[16];
@@ -1377,7 +1407,7 @@ __global__ void __launch_bounds__(256, TGRP ? 4 : (SURE ? ESC_FRAME_SURE_WAVES :
     Hit hit[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      dir[q] = primary_dir(p, T.w0 + T.lx0 + 16 * q, h);
+      dir[q] = primary_dir(p, rays, T.w0 + T.lx0 + 16 * q, h);
       hit[q].t = FLT_MAX; // main.cpp:715
       hit[q].v = 0.f;
       hit[q].idx = -1;
@@ -1873,6 +1903,47 @@ extern "C" int esc_launch_prepare(const esc::RenderParams *p, esc::DevTriP *tri_
   return (int)hipGetLastError();
 }
 
+// k_frame's ray tables (rt_device.h RayTables): W and H entries for p's camera
+extern "C" int esc_launch_ray_tables(const esc::RenderParams *p, esc::RayEntry *col, esc::RayEntry *row,
+                                     hipStream_t stream) {
+  const int n = p->W > p->H ? p->W : p->H;
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(esc::k_prepare_ray_tables, dim3((n + 255) / 256), dim3(256), 0, stream, *p, col, row);
+  return (int)hipGetLastError();
+}
+
+// the test hook esc_check_inv_det_exact: inv_det_exact against the division it stands for, over the
+// float bit patterns first .. first + n - 1 that pass ray_triangle.h:23-25.  out[0]: mismatches;
+// out[1]: the smallest mismatching pattern (the caller starts it at ~0)
+namespace esc {
+__global__ void __launch_bounds__(256) k_check_inv_det(uint32_t first, unsigned long long n, unsigned long long *out) {
+  unsigned long long bad = 0, lowest = ~0ull;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x; i < n;
+       i += (unsigned long long)gridDim.x * 256u) {
+    const uint32_t bits = first + (uint32_t)i;
+    const float x = __uint_as_float(bits);
+    const double eps = (double)FLT_EPSILON, det = (double)x;
+    if (det > -eps && det < eps) continue; // :23-25
+    if (__double_as_longlong(inv_det_exact(x)) != __double_as_longlong(1.0 / det)) {
+      bad++;
+      if (bits < lowest) lowest = bits;
+    }
+  }
+  if (bad) {
+    atomicAdd(&out[0], bad);
+    atomicMin(&out[1], lowest);
+  }
+}
+} // namespace esc
+extern "C" int esc_launch_check_inv_det(uint32_t first, uint64_t n, unsigned long long *out, hipStream_t stream) {
+  if (n == 0) return 0;
+  const uint64_t per_block = 256u * 256u; // 256 patterns per thread
+  const uint64_t blocks = (n + per_block - 1) / per_block;
+  hipLaunchKernelGGL(esc::k_check_inv_det, dim3((unsigned)blocks), dim3(256), 0, stream, first,
+                     (unsigned long long)n, out);
+  return (int)hipGetLastError();
+}
+
 // tile lists of the primary pass (rt_lists.h): hdr / cnt zeroed by the caller on this stream; after
 // esc_launch_prepare (the triangle groups' frame cones)
 extern "C" int esc_launch_tile_lists(const esc::RenderParams *p, hipStream_t stream) {
@@ -2016,8 +2087,9 @@ extern "C" int esc_launch_primary_only(const esc::RenderParams *p, int px, hipSt
 // stage: 1 SMEM (always 2 px), 2 LDS, 3 BVH (px ignored).  px: pixels per work-item of the LDS primary pass (1, 2 or 4); the shade
 // pass always carries one pixel per work-item.
 // *which: the k_frame instantiation launched, as ESC_FRAME_KERNEL_* bits (0: another path)
-extern "C" int esc_launch_render(const esc::RenderParams *p, int stage, int px, hipStream_t stream,
-                                 hipEvent_t between, int two_kernels, int *which) {
+// rays: k_frame's ray tables for this camera and image size (every other path ignores them)
+extern "C" int esc_launch_render(const esc::RenderParams *p, const esc::RayTables *rays, int stage, int px,
+                                 hipStream_t stream, hipEvent_t between, int two_kernels, int *which) {
   *which = 0;
   if (p->n_local_rows <= 0 || p->W <= 0) return 0;
   using esc::v2f;
@@ -2039,6 +2111,7 @@ extern "C" int esc_launch_render(const esc::RenderParams *p, int stage, int px, 
     if (between) (void)hipEventRecord(between, stream);
     hipLaunchKernelGGL((esc::k_shade<esc::STAGE_LDS>), dim3(shade_grid), dim3(256), 0, stream, *p);
   } else if (!two_kernels && !between) { // the whole frame in one kernel (k_frame)
+    if (!rays || !rays->col || !rays->row) return (int)hipErrorInvalidValue; // no tables, no frame
     const dim3 grid((unsigned)((p->W + 63) / 64), (unsigned)tiles_y); // (x, y) = the tile: Tile<2>::Grid2D
     const bool grp = p->use_filter && (p->sg.n_grp > 0 || p->tg.n_grp > 0);
     const bool tgrp = p->use_filter && p->tg.n_grp > 0;
@@ -2049,17 +2122,17 @@ extern "C" int esc_launch_render(const esc::RenderParams *p, int stage, int px, 
     for (int li = 0; sure && li < p->n_lights; ++li) sure = esc::shadow_lists_cover<false>(*p, li);
     *which = 1 | (grp ? 2 : 0) | (tgrp ? 4 : 0) | (idl || !grp ? 8 : 0) | (sure ? 16 : 0);
     if (tgrp && idl)
-      hipLaunchKernelGGL((esc::k_frame<true, true, true>), grid, dim3(256), 0, stream, *p);
+      hipLaunchKernelGGL((esc::k_frame<true, true, true>), grid, dim3(256), 0, stream, *p, *rays);
     else if (tgrp)
-      hipLaunchKernelGGL((esc::k_frame<true, true>), grid, dim3(256), 0, stream, *p);
+      hipLaunchKernelGGL((esc::k_frame<true, true>), grid, dim3(256), 0, stream, *p, *rays);
     else if (grp && idl)
-      hipLaunchKernelGGL((esc::k_frame<true, false, true>), grid, dim3(256), 0, stream, *p);
+      hipLaunchKernelGGL((esc::k_frame<true, false, true>), grid, dim3(256), 0, stream, *p, *rays);
     else if (sure)
-      hipLaunchKernelGGL((esc::k_frame<true, false, false, true>), grid, dim3(256), 0, stream, *p);
+      hipLaunchKernelGGL((esc::k_frame<true, false, false, true>), grid, dim3(256), 0, stream, *p, *rays);
     else if (grp)
-      hipLaunchKernelGGL((esc::k_frame<true, false>), grid, dim3(256), 0, stream, *p);
+      hipLaunchKernelGGL((esc::k_frame<true, false>), grid, dim3(256), 0, stream, *p, *rays);
     else // (no groups: no light lists)
-      hipLaunchKernelGGL((esc::k_frame<false, false, true>), grid, dim3(256), 0, stream, *p);
+      hipLaunchKernelGGL((esc::k_frame<false, false, true>), grid, dim3(256), 0, stream, *p, *rays);
   } else {
     launch_primary<esc::STAGE_SMEM, v2f, 1>(p, stream); // always 2 px: see esc_launch_primary_only
     if (between) (void)hipEventRecord(between, stream);

@@ -90,12 +90,35 @@ DEVINL void pack3(const f3 *src, V3<V> (&dst)[NV]) {
 // exact tails (rare paths)
 // ---------------------------------------------------------------------------------------
 
+// ray_triangle.h:26 `1.0 / det` for a det that is a widened float and has passed :23-25, bit for bit
+// ("The reciprocal of the exact tail").  The compiler's f64 division scales its operands
+// and fixes the quotient up for ranges such a det cannot be in (11 f64 instructions); here v_rcp_f64
+// is refined by two Newton steps with an exact residual, r = 1 - d y, y' = y + r y: the second one
+// lands within r^2 of 1/d before its single rounding, and the reciprocal of a 24-bit d is never that
+// close to a rounding midpoint of 53 bits (a power of two has an exact reciprocal).  |d| lies in
+// [2^-23, 2^128): nothing here over- or underflows.  +-inf and the NaNs also pass :23-25 and the
+// residual of an infinity is a NaN; for them the bare v_rcp_f64 already is the quotient's 64 bits
+// (+-0, the quieted NaN), so a select on the float's exponent keeps it.  (A wave-uniform detour
+// through the plain `/` instead of the select measured SLOWER than the division it replaces: DESIGN.md
+// Appendix A.)  esc_check_inv_det_exact compares all 2^32 patterns with the division on the device.
+DEVINL double inv_det_exact(float detf) {
+  const double d = (double)detf;
+  const double y0 = __builtin_amdgcn_rcp(d);
+  double y = y0;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const double r = __builtin_fma(-d, y, 1.0);
+    y = __builtin_fma(r, y, y);
+  }
+  return (__float_as_uint(detf) & 0x7f800000u) != 0x7f800000u ? y : y0;
+}
+
 // ray_triangle.h:21-46 given the fp32 numerators: every reject except the `t2 >= *t` bound.
 DEVINL bool tri_exact_nb(float detf, float unum, float vnum, float tnum, float &t2o, float &v2o) {
   const double eps = (double)FLT_EPSILON;
   double det = (double)detf;                    // :21
   if (det > -eps && det < eps) return false;    // :23-25
-  double inv_det = 1.0 / det;                   // :26 (1.0f widened)
+  double inv_det = inv_det_exact(detf);         // :26 (1.0f widened)
   float u2 = (float)((double)unum * inv_det);   // :32
   if (u2 < FLT_EPSILON || u2 > 1.0f) return false; // :33
   float v2 = (float)((double)vnum * inv_det);   // :40
@@ -113,7 +136,7 @@ DEVINL bool tri_exact_nb_uv(float detf, float unum, float vnum, float tnum, floa
   const double eps = (double)FLT_EPSILON;
   double det = (double)detf;                    // :21
   if (det > -eps && det < eps) return false;    // :23-25
-  double inv_det = 1.0 / det;                   // :26 (1.0f widened)
+  double inv_det = inv_det_exact(detf);         // :26 (1.0f widened)
   float u2 = (float)((double)unum * inv_det);   // :32
   if (u2 < FLT_EPSILON || u2 > 1.0f) return false; // :33
   float v2 = (float)((double)vnum * inv_det);   // :40

@@ -595,6 +595,15 @@ int esc_last_frame_kernel(esc_context *ctx);
  * refused by the light lists after all -- which the launch conditions rule out: a check for tests, 0
  * always.  Returns 0 or 1, or a negative error.  Synchronises the context's stream. */
 int esc_frame_tripwire(esc_context *ctx);
+/* A check for tests: the exact tail of the triangle test takes 1 / det (ray_triangle.h:26, det a widened
+ * float) from a reciprocal refined by hand instead of the compiler's f64 division.  Runs that helper on
+ * the device over the float bit patterns first_bits .. first_bits + n - 1 (modulo 2^32; n <= 2^32) and
+ * compares it, as 64-bit integers, with 1.0 / (double)x wherever x passes the range test in front of it
+ * (ray_triangle.h:23-25: every |x| >= FLT_EPSILON, the infinities and the NaNs).  *mismatches receives
+ * the number of patterns that differ, *first_mismatch the smallest of them (0 when there is none).
+ * Synchronises the context's stream. */
+int esc_check_inv_det_exact(esc_context *ctx, uint32_t first_bits, uint64_t n, uint64_t *mismatches,
+                            uint32_t *first_mismatch);
 /* Host only: 1 when every shadow-ray origin fl(origin + dir (t - eps)) of a camera at `origin` -- any
  * direction, any primary hit the kernels accept in `scene` -- lies inside the scene's grown box
  * (esc_scene_table_header scene_lo / scene_hi), by the sufficient condition of DESIGN.md 3.9; 0 when the
