@@ -18,7 +18,7 @@ from ._capi import (ESC_FACE_FIXED, ESC_FACE_HASH, ESC_STAGE_AUTO, ESC_STAGE_BVH
                     ESC_STAGE_SMEM, ESC_TRANSMIT_OFF, ESC_TRANSMIT_REFRACT, ESC_TRANSMIT_FRESNEL, EscError,
                     check)
 
-__all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "live_device_allocations", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table", "environment_sky", "environment_lookup_host",
+__all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "TemporalAccumulator", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "live_device_allocations", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table", "environment_sky", "environment_lookup_host",
            "EscError", "ESC_FACE_FIXED", "ESC_FACE_HASH", "ESC_STAGE_AUTO", "ESC_STAGE_SMEM",
            "ESC_STAGE_LDS", "ESC_STAGE_BVH", "ESC_RENDER_EXACT_ONLY", "ESC_RENDER_TIME_KERNELS", "ESC_RENDER_INDEX_ORDER", "ESC_RENDER_SHADE_QUEUE",
            "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "ESC_RENDER_NO_PACKED_LIGHT_LISTS", "ESC_RENDER_VOTE", "ESC_TRANSMIT_OFF", "ESC_TRANSMIT_REFRACT", "ESC_TRANSMIT_FRESNEL", "version"]
@@ -983,6 +983,78 @@ class Renderer:
         check(self._lib.esc_last_filter_stats(self._h, C.byref(s)))
         return {k: int(getattr(s, k)) for k in ("pixels", "hit_pixels", "taps_tested", "taps_accepted")}
 
+    # ---- temporal accumulation (esc_temporal_accumulate) -------------------------------------------------
+    def _guide_tensors(self, name, guides, H, W):
+        """-> the four guide arrays as contiguous device tensors of a (H, W) frame, and an esc_guides of them"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        t = {}
+        for k, dt, c in (("normal", torch.float32, 3), ("position", torch.float32, 3), ("geom", torch.int32, 0),
+                         ("prim", torch.int32, 0)):
+            g = guides[k]
+            if not isinstance(g, torch.Tensor):
+                g = torch.from_numpy(np.array(g, dtype=np.float32 if c else np.int32, order="C")).to(dev)
+            g = g.reshape((H, W, 3) if c else (H, W))
+            self._query_ptr(f"{name}[{k!r}]", g, dt, (H, W, 3) if c else (H, W))
+            t[k] = g
+        return t, _capi.esc_guides(*[t[k].data_ptr() for k in ("normal", "position", "geom", "prim")])
+
+    def temporal_accumulate(self, image, guides, prev_camera, history, history_n, prev_guides, *, taps=4,
+                            max_history=32, normal_cos=0.9, plane_dist, same_object=True, out=None, out_n=None):
+        """Temporal accumulation (esc_temporal_accumulate): every hit pixel of `image`, (H, W) or (H, W, 3)
+        float32 with the guides of its frame, is looked up in the previous frame -- rendered with prev_camera at
+        the same size, whose accumulated image is `history`, whose history lengths are `history_n` (H, W) int32
+        and whose guides are prev_guides -- through `taps` = 1 (nearest) or 4 (bilinear) history pixels, which
+        count under the stops of filter_guided, and blended with alpha = 1 / n, n at most max_history.  A first
+        frame is the call with history_n all zero.  guides, prev_guides: dicts as render_gbuffer returns them
+        ("normal", "position", "geom", "prim" are read).  Arrays may be numpy arrays or contiguous device
+        tensors.  Returns (out, out_n): numpy arrays for a numpy image (synchronous); for a device tensor
+        device tensors (`out` / `out_n`, or new ones), asynchronous on the renderer's stream.  out may be
+        image, but not history, and out_n not history_n."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        as_numpy = not isinstance(image, torch.Tensor)
+        img = torch.from_numpy(np.array(image, dtype=np.float32, order="C")).to(dev) if as_numpy else image
+        if img.dim() not in (2, 3) or (img.dim() == 3 and img.shape[2] != 3):
+            raise ValueError("image must have shape (H, W) or (H, W, 3)")
+        H, W = int(img.shape[0]), int(img.shape[1])
+        ch = 3 if img.dim() == 3 else 1
+        pi = self._query_ptr("image", img, torch.float32, tuple(img.shape))
+        hist = history
+        if not isinstance(hist, torch.Tensor):
+            hist = torch.from_numpy(np.array(hist, dtype=np.float32, order="C")).to(dev)
+        hn = history_n
+        if not isinstance(hn, torch.Tensor):
+            hn = torch.from_numpy(np.array(hn, dtype=np.int32, order="C")).to(dev)
+        ph = self._query_ptr("history", hist, torch.float32, tuple(img.shape))
+        phn = self._query_ptr("history_n", hn, torch.int32, (H, W))
+        tc, gc = self._guide_tensors("guides", guides, H, W)
+        tp, gp = self._guide_tensors("prev_guides", prev_guides, H, W)
+        if out is None:
+            out = torch.empty_like(img)
+        if out_n is None:
+            out_n = torch.empty((H, W), dtype=torch.int32, device=dev)
+        po = self._query_ptr("out", out, torch.float32, tuple(img.shape))
+        pon = self._query_ptr("out_n", out_n, torch.int32, (H, W))
+        o = _capi.esc_temporal_options(int(taps), int(max_history), float(normal_cos), float(plane_dist),
+                                       int(bool(same_object)))
+        torch.cuda.current_stream(dev).synchronize()  # copies and buffers were made on torch's stream
+        check(self._lib.esc_temporal_accumulate(self._h, C.byref(prev_camera.c), W, H, ch, pi, C.byref(gc), ph, phn,
+                                                C.byref(gp), C.byref(o), po, pon))
+        if as_numpy:
+            self.synchronize()
+            return out.cpu().numpy(), out_n.cpu().numpy()
+        self._temporal_keep = (img, hist, hn, tc, tp)  # alive until the next call: the launch is asynchronous
+        return out, out_n
+
+    def temporal_stats(self):
+        """Counts of the last temporal_accumulate call: pixels, hit_pixels, reused_pixels, taps_tested and
+        taps_accepted.  Synchronises."""
+        s = _capi.esc_temporal_stats()
+        check(self._lib.esc_last_temporal_stats(self._h, C.byref(s)))
+        return {k: int(getattr(s, k)) for k in ("pixels", "hit_pixels", "reused_pixels", "taps_tested",
+                                                "taps_accepted")}
+
     # ---- environment cube map (esc_set_environment / esc_environment_rays) ------------------------------
     def set_environment(self, cube):
         """esc_set_environment: cube is a (6, R, R, 3) float32 array, faces +x, -x, +y, -y, +z, -z
@@ -1212,6 +1284,63 @@ class RecordedFrame:
 
     def __del__(self):
         self.close()
+
+
+class TemporalAccumulator:
+    """Frame-to-frame state of Renderer.temporal_accumulate: the previous frame's camera, guides, accumulated
+    image and history lengths, kept as device tensors.  The accumulated image and the lengths alternate
+    between two buffers each, so no push reads what it writes.  options: temporal_accumulate's keywords
+    (taps, max_history, normal_cos, plane_dist, same_object); plane_dist is required."""
+
+    def __init__(self, renderer, **options):
+        unknown = set(options) - {"taps", "max_history", "normal_cos", "plane_dist", "same_object"}
+        if unknown:
+            raise TypeError(f"unknown options: {sorted(unknown)}")
+        if "plane_dist" not in options:
+            raise TypeError("plane_dist is required")
+        self._r, self._opts = renderer, dict(options)
+        self.reset()
+
+    def reset(self):
+        """forget the history: the next push starts from zero"""
+        self._camera = self._guides = None
+        self._acc, self._n, self._at = [None, None], [None, None], 0
+
+    @property
+    def history_n(self):
+        """the history lengths after the last push, a (H, W) int32 device tensor, or None before the first"""
+        return self._n[self._at]
+
+    def push(self, camera, image, guides):
+        """Accumulate one frame: image (H, W) or (H, W, 3) float32 and its guides (render_gbuffer's dict), both
+        numpy arrays or device tensors, rendered with `camera`.  The first push, or an image of another shape,
+        starts from zero history.  Returns the accumulated image: a numpy array for a numpy image
+        (synchronous), else the accumulator's own device tensor (asynchronous on the renderer's stream), which
+        the push after the next one overwrites.  Guide tensors are kept until the next push, not copied."""
+        import torch
+        r = self._r
+        dev = torch.device("cuda", r.device)
+        as_numpy = not isinstance(image, torch.Tensor)
+        img = torch.from_numpy(np.array(image, dtype=np.float32, order="C")).to(dev) if as_numpy else image
+        if img.dim() not in (2, 3) or (img.dim() == 3 and img.shape[2] != 3):
+            raise ValueError("image must have shape (H, W) or (H, W, 3)")
+        H, W = int(img.shape[0]), int(img.shape[1])
+        cur, _ = r._guide_tensors("guides", guides, H, W)
+        acc = self._acc[self._at]
+        if acc is None or acc.shape != img.shape:
+            self.reset()
+            self._acc = [torch.zeros_like(img), torch.empty_like(img)]
+            self._n = [torch.zeros((H, W), dtype=torch.int32, device=dev),
+                       torch.empty((H, W), dtype=torch.int32, device=dev)]
+            self._camera, self._guides = camera, cur
+        to = 1 - self._at
+        r.temporal_accumulate(img, cur, self._camera, self._acc[self._at], self._n[self._at], self._guides,
+                              out=self._acc[to], out_n=self._n[to], **self._opts)
+        self._at, self._camera, self._guides = to, camera, cur
+        if as_numpy:
+            r.synchronize()
+            return self._acc[to].cpu().numpy()
+        return self._acc[to]
 
 
 def live_device_allocations():

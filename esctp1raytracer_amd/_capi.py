@@ -160,6 +160,20 @@ class esc_filter_stats(C.Structure):  # 32 bytes
                 ("taps_accepted", C.c_uint64)]
 
 
+class esc_guides(C.Structure):  # 32 bytes: four device pointers
+    _fields_ = [("normal", C.c_void_p), ("position", C.c_void_p), ("geom", C.c_void_p), ("prim", C.c_void_p)]
+
+
+class esc_temporal_options(C.Structure):  # 32 bytes
+    _fields_ = [("taps", C.c_int32), ("max_history", C.c_int32), ("normal_cos", C.c_float),
+                ("plane_dist", C.c_float), ("same_object", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class esc_temporal_stats(C.Structure):  # 40 bytes
+    _fields_ = [("pixels", C.c_uint64), ("hit_pixels", C.c_uint64), ("reused_pixels", C.c_uint64),
+                ("taps_tested", C.c_uint64), ("taps_accepted", C.c_uint64)]
+
+
 class esc_bvh_node(C.Structure):  # 64 bytes
     _fields_ = [("lo0", C.c_float * 3), ("hi0", C.c_float * 3), ("lo1", C.c_float * 3),
                 ("hi1", C.c_float * 3), ("child", C.c_int32 * 2), ("minkey", C.c_uint32 * 2)]
@@ -300,6 +314,10 @@ SIGNATURES = {
     "esc_filter_guided": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                     C.POINTER(esc_filter_options), _P]),
     "esc_last_filter_stats": (C.c_int, [_P, C.POINTER(esc_filter_stats)]),
+    "esc_temporal_accumulate": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32, C.c_int32, _P,
+                                          C.POINTER(esc_guides), _P, _P, C.POINTER(esc_guides),
+                                          C.POINTER(esc_temporal_options), _P, _P]),
+    "esc_last_temporal_stats": (C.c_int, [_P, C.POINTER(esc_temporal_stats)]),
     "esc_set_environment": (C.c_int, [_P, C.c_int32, _F]),
     "esc_get_environment_res": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "esc_environment_sky": (C.c_int, [C.c_int32, _F, _F, _F, _F]),

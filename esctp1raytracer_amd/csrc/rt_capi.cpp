@@ -26,6 +26,7 @@
 #include "rt_gbuffer.h"
 #include "rt_query.h"
 #include "rt_shade_rays.h"
+#include "rt_temporal.h"
 #include "rt_trace.h"
 #include "rt_tile_math.h"
 
@@ -73,6 +74,8 @@ extern "C" int esc_launch_modulate(const esc::ModulateParams *p, hipStream_t str
 extern "C" int esc_launch_gbuffer(const esc::GBufferParams *p, int camera, hipStream_t stream);
 extern "C" int esc_launch_filter_pack(const esc::FilterPackParams *p, hipStream_t stream);
 extern "C" int esc_launch_filter_atrous(const esc::FilterParams *p, int channels, int64_t tiles, hipStream_t stream);
+extern "C" int esc_launch_temporal(const esc::TemporalParams *p, int channels, int taps, int64_t tiles,
+                                   hipStream_t stream);
 extern "C" int esc_launch_assemble(const void *gathered, void *frame, size_t rank_pitch_bytes,
                                    int n_ranks, int H, int strip_rows, size_t row_bytes,
                                    hipStream_t stream);
@@ -251,6 +254,10 @@ struct esc_context {
   size_t fl_guide_cap = 0;
   float *d_fl_img = nullptr;
   size_t fl_img_cap = 0;
+  // esc_temporal_accumulate (rt_temporal.hip): esc_temporal_stats' device counters (kTemporalStatSets replicas
+  // of 8 words, summed on read) and the last call's W*H
+  unsigned long long *d_tpstats = nullptr;
+  uint64_t tp_pixels = 0;
 };
 
 // ---- rt_devmem.h's backend: the only hipMalloc / hipFree of this file
@@ -3367,6 +3374,140 @@ int esc_last_filter_stats(esc_context *ctx, esc_filter_stats *out) {
   out->hit_pixels = h[0];
   out->taps_tested = h[1];
   out->taps_accepted = h[2];
+  return ESC_OK;
+}
+
+// ---- temporal accumulation (rt_temporal.hip) -----------------------------------------
+int esc_temporal_accumulate(esc_context *ctx, const esc_camera *prev_cam, int32_t W, int32_t H, int32_t channels,
+                            const float *d_current, const esc_guides *cur, const float *d_history,
+                            const int32_t *d_history_n, const esc_guides *prev, const esc_temporal_options *opts,
+                            float *d_out, int32_t *d_out_n) {
+  const std::string fn("esc_temporal_accumulate");
+  if (!ctx || !opts || !prev_cam || !cur || !prev) {
+    set_error(fn + (!ctx ? ": ctx is null" : !opts ? ": opts is null" : !prev_cam ? ": prev_cam is null"
+                    : !cur ? ": cur is null" : ": prev is null"));
+    return ESC_ERR_INVALID;
+  }
+  if (W < 2 || H < 2) {
+    set_error(fn + ": need W,H >= 2");
+    return ESC_ERR_INVALID;
+  }
+  if (channels != 1 && channels != 3) {
+    set_error(fn + ": channels must be 1 or 3");
+    return ESC_ERR_INVALID;
+  }
+  if (opts->taps != 1 && opts->taps != 4) {
+    set_error(fn + ": taps must be 1 or 4");
+    return ESC_ERR_INVALID;
+  }
+  if (opts->max_history < 1 || opts->max_history > esc::kTemporalMaxHistory) {
+    set_error(fn + ": max_history must be in 1 .. 65536");
+    return ESC_ERR_INVALID;
+  }
+  if (std::isnan(opts->normal_cos)) {
+    set_error(fn + ": normal_cos must not be NaN");
+    return ESC_ERR_INVALID;
+  }
+  if (!(opts->plane_dist >= 0.f)) {
+    set_error(fn + ": plane_dist must be >= 0 and not NaN (FLT_MAX or inf: off)");
+    return ESC_ERR_INVALID;
+  }
+  if (opts->same_object != 0 && opts->same_object != 1) {
+    set_error(fn + ": same_object must be 0 or 1");
+    return ESC_ERR_INVALID;
+  }
+  if (opts->reserved[0] || opts->reserved[1] || opts->reserved[2]) {
+    set_error(fn + ": reserved must be 0");
+    return ESC_ERR_INVALID;
+  }
+  if (!d_current || !d_history || !d_history_n || !d_out || !d_out_n) {
+    set_error(fn + ": d_current, d_history, d_history_n, d_out and d_out_n are required");
+    return ESC_ERR_INVALID;
+  }
+  for (int k = 0; k < 2; k++) {
+    const esc_guides *g = k ? prev : cur;
+    if (!g->normal || !g->position || !g->geom || !g->prim) {
+      set_error(fn + (k ? ": prev" : ": cur") + "'s normal, position, geom and prim are required");
+      return ESC_ERR_INVALID;
+    }
+    if (((uintptr_t)g->normal | (uintptr_t)g->position | (uintptr_t)g->geom | (uintptr_t)g->prim) & 3u) {
+      set_error(fn + (k ? ": prev" : ": cur") + "'s device pointers must be 4-byte aligned");
+      return ESC_ERR_INVALID;
+    }
+  }
+  if (d_out == d_history) {
+    set_error(fn + ": d_out must not be d_history");
+    return ESC_ERR_INVALID;
+  }
+  if (d_out_n == d_history_n) {
+    set_error(fn + ": d_out_n must not be d_history_n");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_current | (uintptr_t)d_history | (uintptr_t)d_history_n | (uintptr_t)d_out |
+       (uintptr_t)d_out_n) & 3u) {
+    set_error(fn + ": d_current, d_history, d_history_n, d_out and d_out_n must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  const int64_t tiles_x = ((int64_t)W + esc::kTemporalTileW - 1) / esc::kTemporalTileW;
+  const int64_t tiles = tiles_x * (((int64_t)H + esc::kTemporalTileH - 1) / esc::kTemporalTileH);
+  if (tiles > (int64_t)0x7fffffff) {
+    set_error(fn + ": W*H exceeds one launch (2^31 - 1 tiles of 64 x 4 pixels)");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!ctx->d_tpstats && ctx->call.alloc(ctx->d_tpstats, (size_t)esc::kTemporalStatSets * 8)) return ESC_ERR_HIP;
+  HIP_TRY(hipMemsetAsync(ctx->d_tpstats, 0, esc::kTemporalStatSets * 8 * sizeof(unsigned long long), ctx->stream));
+  ctx->tp_pixels = (uint64_t)W * (uint64_t)H;
+  esc::TemporalParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.W = W;
+  p.H = H;
+  p.same_object = opts->same_object;
+  p.max_history = opts->max_history;
+  p.normal_cos = opts->normal_cos;
+  p.plane_dist = opts->plane_dist;
+  for (int k = 0; k < 3; k++) {
+    p.origin[k] = prev_cam->origin[k];
+    p.lower_left_corner[k] = prev_cam->lower_left_corner[k];
+    p.horizontal[k] = prev_cam->horizontal[k];
+    p.vertical[k] = prev_cam->vertical[k];
+  }
+  p.tiles_x = tiles_x;
+  p.current = d_current;
+  p.cur = {cur->normal, cur->position, cur->geom, cur->prim};
+  p.prev = {prev->normal, prev->position, prev->geom, prev->prim};
+  p.history = d_history;
+  p.history_n = d_history_n;
+  p.out = d_out;
+  p.out_n = d_out_n;
+  p.stats = ctx->d_tpstats;
+  const int rc = esc_launch_temporal(&p, channels, opts->taps, tiles, ctx->stream);
+  if (rc) {
+    set_error(fn + ": k_temporal launch: " + hipGetErrorString((hipError_t)rc));
+    return ESC_ERR_HIP;
+  }
+  return ESC_OK;
+}
+
+int esc_last_temporal_stats(esc_context *ctx, esc_temporal_stats *out) {
+  if (!ctx || !out) {
+    set_error(!ctx ? "esc_last_temporal_stats: ctx is null" : "esc_last_temporal_stats: out is null");
+    return ESC_ERR_INVALID;
+  }
+  unsigned long long h[esc::kTemporalStats] = {0, 0, 0, 0};
+  if (ctx->d_tpstats) {
+    unsigned long long all[esc::kTemporalStatSets * 8];
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(all, ctx->d_tpstats, sizeof(all), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int s = 0; s < esc::kTemporalStatSets; s++)
+      for (int j = 0; j < esc::kTemporalStats; j++) h[j] += all[s * 8 + j];
+  }
+  out->pixels = ctx->d_tpstats ? ctx->tp_pixels : 0;
+  out->hit_pixels = h[0];
+  out->reused_pixels = h[1];
+  out->taps_tested = h[2];
+  out->taps_accepted = h[3];
   return ESC_OK;
 }
 

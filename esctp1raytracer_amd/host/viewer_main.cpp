@@ -55,6 +55,15 @@
 //                 (default 0.9)
 //   --denoise-plane X   with --denoise: ... and it lies within X (>= 0) of the pixel's tangent plane (default
 //                 --ao-radius / 4)
+//   --temporal N  with --ao: N (1..64) frames are rendered and the visibility (--skylight: the light) is
+//                 accumulated over them (esc_render_gbuffer, esc_temporal_accumulate).  Frame f = 0 .. N-1 has
+//                 its eye at the view's (-v) minus --temporal-step times (N-1-f), per component in fp32, so the
+//                 last frame is the given view; the look-at stays; the AO seed of frame f is f (not with --ao-seed).  The stops are
+//                 --denoise-normal / --denoise-plane with --denoise's defaults; --denoise L filters the
+//                 accumulated image of the last frame
+//   --temporal-step x,y,z   with --temporal: how far the eye moves per frame (finite; default 0,0,0)
+//   --temporal-max M   with --temporal: the history length saturates at M (1..65536, default 32)
+//   --temporal-taps T  with --temporal: 1 = the nearest history pixel, 4 = bilinear (default)
 //   --sky Z/H/G   environment: a vertical gradient (zenith, horizon, ground colours, each r,g,b; finite) that
 //                 the rays which leave the scene see, primary rays and bounces alike (esc_environment_sky,
 //                 esc_set_environment).  The frame is rendered through esc_render_traced_ex, at depth 0 when
@@ -117,6 +126,10 @@ const char *kUsage =
     "  --ao-sets S --ao-bias B --ao-seed N   with --ao: direction sets (16), surface offset (1e-4), seed (0)\n"
     "  --denoise L                with --ao: L (1..8) passes of the edge-stopping filter over vis / light\n"
     "  --denoise-normal C --denoise-plane X   with --denoise: normal (0.9) and plane (--ao-radius / 4) stops\n"
+    "  --temporal N               with --ao: accumulate vis / light over N (1..64) frames, frame f seeded with f;\n"
+    "                             the stops are --denoise-normal / --denoise-plane, --denoise filters the result\n"
+    "  --temporal-step x,y,z --temporal-max M --temporal-taps 1|4   with --temporal: the eye's move per frame\n"
+    "                             (0,0,0; the last frame is the -v view), the longest history (32), taps (4)\n"
     "  --sky zr,zg,zb/hr,hg,hb/gr,gg,gb   rays that leave the scene see a zenith / horizon / ground gradient\n"
     "  --sky-res N                with --sky: texels per side of the environment cube (1..1024, default 64)\n"
     "  --skylight                 with --sky and --ao K --ao-radius R: add the sky's light on the open directions\n"
@@ -159,6 +172,20 @@ void parse_sky(const char *next, float out[9]) {
   }
 }
 
+// --temporal-step's value: three finite numbers separated by ','
+void parse_step(const char *next, float out[3]) {
+  const std::string err = "--temporal-step needs x,y,z with three finite numbers";
+  if (!next) die(err);
+  const char *p = next;
+  for (int k = 0; k < 3; ++k) {
+    char *end = nullptr;
+    const float v = std::strtof(p, &end);
+    if (end == p || !std::isfinite(v) || *end != (k == 2 ? '\0' : ',')) die(err + ", got " + next);
+    out[k] = v;
+    p = end + 1;
+  }
+}
+
 } // namespace
 
 int main(int argc, char *argv[]) {
@@ -180,6 +207,9 @@ int main(int argc, char *argv[]) {
   int denoise = 0;
   float denoise_normal = 0.9f, denoise_plane = 0.f;
   bool have_denoise_extra = false, have_denoise_plane = false;
+  int temporal = 0, temporal_max = 32, temporal_taps = 4;
+  float temporal_step[3] = {0.f, 0.f, 0.f};
+  bool have_temporal_extra = false, have_ao_seed = false;
   float sky_colours[9] = {0};
   int sky_res = 64;
 
@@ -284,7 +314,29 @@ int main(int argc, char *argv[]) {
       char *end = nullptr;
       ao_seed = std::strtoull(next, &end, 0);
       if (end == next || *end != '\0') die(std::string("--ao-seed must be a whole number, got ") + next);
-      have_ao_extra = true;
+      have_ao_extra = have_ao_seed = true;
+      arg++;
+      continue;
+    }
+    if (a == "--temporal") { temporal = (int)parse_whole("--temporal", next, 1, 64); arg++; continue; }
+    if (a == "--temporal-step") {
+      parse_step(next, temporal_step);
+      have_temporal_extra = true;
+      arg++;
+      continue;
+    }
+    if (a == "--temporal-max") {
+      temporal_max = (int)parse_whole("--temporal-max", next, 1, 65536);
+      have_temporal_extra = true;
+      arg++;
+      continue;
+    }
+    if (a == "--temporal-taps") {
+      if (!next) die("--temporal-taps needs a value");
+      if (std::strcmp(next, "1") != 0 && std::strcmp(next, "4") != 0)
+        die(std::string("--temporal-taps must be 1 or 4, got ") + next);
+      temporal_taps = next[0] - '0';
+      have_temporal_extra = true;
       arg++;
       continue;
     }
@@ -338,7 +390,10 @@ int main(int argc, char *argv[]) {
   if (!ao && (have_ao_radius || have_ao_extra)) die("--ao-radius, --ao-sets, --ao-bias and --ao-seed need --ao");
   if (ao && (ispc || gpus != 1)) die("--ao renders on one GPU and not with --ispc");
   if (denoise && !ao) die("--denoise needs --ao");
-  if (!denoise && have_denoise_extra) die("--denoise-normal and --denoise-plane need --denoise");
+  if (temporal && !ao) die("--temporal needs --ao");
+  if (!temporal && have_temporal_extra) die("--temporal-step, --temporal-max and --temporal-taps need --temporal");
+  if (temporal && have_ao_seed) die("--temporal seeds frame f with f: not with --ao-seed");
+  if (!denoise && !temporal && have_denoise_extra) die("--denoise-normal and --denoise-plane need --denoise");
   if (have_sky_res && !sky) die("--sky-res needs --sky");
   if (sky && (ispc || flat || gpus != 1)) die("--sky renders on one GPU and not with --ispc, --bvh or --bvh-tree");
   if (sky && have_adaptive) die("--sky is seen by traced frames: not with --adaptive");
@@ -479,39 +534,85 @@ int main(int argc, char *argv[]) {
   if (ao) {
     // the frame back on the device, the pixel centres' visibility (--skylight: the sky's light on them), the
     // product (the sum) in place, and home again
-    std::vector<float> table((size_t)ao_sets * ao * 3);
-    check(esc_ambient_cosine_table(ao_sets, ao, ao_seed, table.data()), "ambient table");
-    check(esc_set_ambient_table(ctx, ao_sets, ao, table.data()), "ambient table");
-    const esc_ambient_options ao_opts = {ao, ao_sets, ao_radius, ao_bias, ao_seed, 0u, 0u};
+    const size_t n = (size_t)W * H, ch = skylight ? 3 : 1;
     float *d_image = nullptr, *d_vis = nullptr; // d_vis: W*H visibilities, or with --skylight W*H*3 of light
     if (hipMalloc((void **)&d_image, image.size() * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&d_vis, (size_t)W * H * (skylight ? 3 : 1) * sizeof(float)) != hipSuccess)
+        hipMalloc((void **)&d_vis, n * ch * sizeof(float)) != hipSuccess)
       die("out of device memory");
     if (hipMemcpy(d_image, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
       die("copy to the device failed");
-    if (skylight) check(esc_render_skylight(ctx, &cam, W, H, &ao_opts, nullptr, d_vis, nullptr, nullptr), "skylight");
-    else check(esc_render_ambient(ctx, &cam, W, H, &ao_opts, d_vis, nullptr), "ambient");
-    float *d_guides = nullptr, *d_filtered = nullptr;
+    // --denoise, --temporal: a frame's guides (normal, position | geom, prim); --temporal keeps the previous
+    // frame's too, and alternates the accumulated image and the history lengths between two buffers each
+    float *d_guides[2] = {nullptr, nullptr}, *d_acc[2] = {nullptr, nullptr}, *d_filtered = nullptr;
+    int32_t *d_n[2] = {nullptr, nullptr};
+    for (int k = 0; k < (temporal ? 2 : denoise ? 1 : 0); ++k)
+      if (hipMalloc((void **)&d_guides[k], n * 8 * sizeof(float)) != hipSuccess) die("out of device memory");
+    if (temporal) {
+      for (int k = 0; k < 2; ++k)
+        if (hipMalloc((void **)&d_acc[k], n * ch * sizeof(float)) != hipSuccess ||
+            hipMalloc((void **)&d_n[k], n * sizeof(int32_t)) != hipSuccess)
+          die("out of device memory");
+      // the first frame's history: no length anywhere
+      if (hipMemset(d_acc[0], 0, n * ch * sizeof(float)) != hipSuccess ||
+          hipMemset(d_n[0], 0, n * sizeof(int32_t)) != hipSuccess)
+        die("clearing the history failed");
+    }
+    const float stop_plane = have_denoise_plane ? denoise_plane : ao_radius / 4.f;
+    const auto guides_of = [n](float *g) {
+      int32_t *geom = reinterpret_cast<int32_t *>(g + 6 * n);
+      return esc_guides{g, g + 3 * n, geom, geom + n};
+    };
     const float *d_use = d_vis;
+    esc_camera prev_cam = cam;
+    const int frames = temporal ? temporal : 1;
+    for (int f = 0; f < frames; ++f) {
+      esc_camera fcam = cam;
+      unsigned long long fseed = ao_seed;
+      if (temporal) { // the eye of frame f; the last frame is the given view
+        float feye[3];
+        for (int k = 0; k < 3; ++k) feye[k] = eye[k] - temporal_step[k] * float(frames - 1 - f);
+        esc_camera_init(&fcam, feye, look, vup, vfov, aspect);
+        fseed = (unsigned long long)f;
+      }
+      std::vector<float> table((size_t)ao_sets * ao * 3);
+      check(esc_ambient_cosine_table(ao_sets, ao, fseed, table.data()), "ambient table");
+      check(esc_set_ambient_table(ctx, ao_sets, ao, table.data()), "ambient table");
+      const esc_ambient_options ao_opts = {ao, ao_sets, ao_radius, ao_bias, fseed, 0u, 0u};
+      if (skylight) check(esc_render_skylight(ctx, &fcam, W, H, &ao_opts, nullptr, d_vis, nullptr, nullptr), "skylight");
+      else check(esc_render_ambient(ctx, &fcam, W, H, &ao_opts, d_vis, nullptr), "ambient");
+      float *g = d_guides[f & 1];
+      if (g) {
+        const esc_guides gs = guides_of(g);
+        check(esc_render_gbuffer(ctx, &fcam, W, H, 0u, g, g + 3 * n, nullptr, nullptr,
+                                 const_cast<int32_t *>(gs.geom), const_cast<int32_t *>(gs.prim)), "gbuffer");
+      }
+      if (temporal) {
+        const esc_guides cur = guides_of(g), prev = f ? guides_of(d_guides[(f & 1) ^ 1]) : cur;
+        const esc_camera pc = f ? prev_cam : fcam;
+        const esc_temporal_options t_opts = {temporal_taps, temporal_max, denoise_normal, stop_plane, 1, {0, 0, 0}};
+        check(esc_temporal_accumulate(ctx, &pc, W, H, (int32_t)ch, d_vis, &cur, d_acc[f & 1], d_n[f & 1], &prev,
+                                      &t_opts, d_acc[(f & 1) ^ 1], d_n[(f & 1) ^ 1]), "temporal");
+        d_use = d_acc[(f & 1) ^ 1];
+        prev_cam = fcam;
+      }
+    }
     if (denoise) {
-      // --denoise: the frame's guides (normal, position | geom, prim), then the filter on vis / light
-      const size_t n = (size_t)W * H, ch = skylight ? 3 : 1;
-      if (hipMalloc((void **)&d_guides, n * 8 * sizeof(float)) != hipSuccess ||
-          hipMalloc((void **)&d_filtered, n * ch * sizeof(float)) != hipSuccess)
-        die("out of device memory");
-      float *d_normal = d_guides, *d_position = d_guides + 3 * n;
-      int32_t *d_geom = reinterpret_cast<int32_t *>(d_guides + 6 * n), *d_prim = d_geom + n;
-      check(esc_render_gbuffer(ctx, &cam, W, H, 0u, d_normal, d_position, nullptr, nullptr, d_geom, d_prim), "gbuffer");
-      const esc_filter_options f_opts = {denoise, denoise_normal, have_denoise_plane ? denoise_plane : ao_radius / 4.f,
-                                         1, {0, 0}};
-      check(esc_filter_guided(ctx, W, H, (int32_t)ch, d_vis, d_normal, d_position, d_geom, d_prim, &f_opts, d_filtered),
-            "denoise");
+      // --denoise: the filter on vis / light, or on what --temporal accumulated, under the last frame's guides
+      if (hipMalloc((void **)&d_filtered, n * ch * sizeof(float)) != hipSuccess) die("out of device memory");
+      const esc_guides gs = guides_of(d_guides[(frames - 1) & 1]);
+      const esc_filter_options f_opts = {denoise, denoise_normal, stop_plane, 1, {0, 0}};
+      check(esc_filter_guided(ctx, W, H, (int32_t)ch, d_use, gs.normal, gs.position, gs.geom, gs.prim, &f_opts,
+                              d_filtered), "denoise");
       d_use = d_filtered;
     }
     if (skylight) check(esc_add_light(ctx, (int64_t)W * H, d_image, d_use, d_image, nullptr), "add light");
     else check(esc_modulate(ctx, (int64_t)W * H, d_image, d_use, d_image, nullptr), "modulate");
     check(esc_context_synchronize(ctx), "ambient");
-    (void)hipFree(d_guides);
+    for (int k = 0; k < 2; ++k) {
+      (void)hipFree(d_guides[k]);
+      (void)hipFree(d_acc[k]);
+      (void)hipFree(d_n[k]);
+    }
     (void)hipFree(d_filtered);
     if (hipMemcpy(image.data(), d_image, image.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
       die("copy back failed");

@@ -1083,7 +1083,8 @@ int esc_last_gbuffer_stats(esc_context *ctx, esc_gbuffer_stats *out);
  * asynchronous on the stream with no host synchronisation.  It needs no scene.
  * ESC_ERR_INVALID: iterations outside 1..8, channels other than 1 or 3, a NaN threshold, a negative
  * plane_dist, same_object other than 0 / 1, a non-zero reserved, W or H < 1, a null or misaligned pointer.
- * Out of scope: temporal accumulation, variance-guided weights, any smooth weight, albedo demodulation. */
+ * Out of scope: variance-guided weights, any smooth weight, albedo demodulation.  Accumulation over frames is
+ * esc_temporal_accumulate, below. */
 typedef struct esc_filter_options {
   int32_t iterations;  /* L, 1..8: iteration i uses step 2^i pixels */
   float normal_cos;    /* a tap needs dot(N_p, N_q) >= normal_cos; not NaN */
@@ -1102,6 +1103,98 @@ int esc_filter_guided(esc_context *ctx, int32_t W, int32_t H, int32_t channels, 
                       const esc_filter_options *opts, float *d_out);
 /* counts of the last esc_filter_guided call (zero before the first); synchronises the context's stream */
 int esc_last_filter_stats(esc_context *ctx, esc_filter_stats *out);
+
+/* ---- temporal accumulation: reproject ambient and sky light from the previous frame (rt_temporal.hip,
+ * DESIGN.md section 3.21) ----
+ * The filter above spreads a frame's K samples per pixel over space; this call keeps them over time.  Every hit
+ * pixel's world-space point is looked up in the previous frame: where the previous camera saw that point, and
+ * whether it is still the same surface there.  If so, the new estimate is blended into what was accumulated,
+ * so a caller with a moving camera can run few samples per frame with a new seed each frame, and a still
+ * camera refines progressively.  It consists of + - * /, floorf and compares: no transcendental, and the
+ * history taps are accepted or rejected by the filter's hard compares, so the result is comparable bit for bit.
+ *
+ * Images are interleaved (channels = 1 or 3 floats per pixel) and pixel (w, h) is at h*W + w, in the images,
+ * in d_history_n / d_out_n and in the guide arrays.  cur holds the guides of the frame that produced
+ * d_current; prev, d_history and d_history_n belong to the previous frame, rendered with prev_cam at the same
+ * W x H.  The current camera is not needed: position is a world-space point.  hit(.) is the filter's,
+ * geom >= 0 || prim >= 0.  All arithmetic is fp32 with one rounding per written operation; dot, cross and the
+ * vector + - * are in vec.h's operation order.  With M = max_history, for pixel p = (w, h):
+ *
+ *   if !hit_cur(p):  out[p] = current[p] (copied, bit for bit);  out_n[p] = 0
+ *   else:
+ *     A = prev_cam.lower_left_corner - prev_cam.origin;   Hh = prev_cam.horizontal;   V = prev_cam.vertical
+ *     v = P_p - prev_cam.origin                                   (per component)
+ *     c   = cross(V, v);          det = dot(Hh, c)
+ *     x   = dot(A, c) / det;      y = dot(Hh, cross(A, v)) / det;      z = dot(Hh, cross(V, A)) / det
+ *           (x Hh + y V + z v = A: the previous camera's ray through s = -x, t = -y passes through P_p,
+ *            in front of the camera iff z > 0)
+ *     fx  = (-x) * float(W - 1);  fy = (-y) * float(H - 1)        (the inverse of s = w/(W-1), t = h/(H-1))
+ *     valid = z > 0 && fx >= -1.f && fx <= float(W) && fy >= -1.f && fy <= float(H)      (a NaN anywhere: false)
+ *     acc_c = +0;  ws = +0;  n = INT32_MAX
+ *     if valid:
+ *       taps == 1:  x0 = floorf(fx + 0.5f);  y0 = floorf(fy + 0.5f);  one tap (i, j) = (0, 0) with k = 1.f
+ *       taps == 4:  x0 = floorf(fx);  ax = fx - x0;  y0 = floorf(fy);  ay = fy - y0
+ *                   taps (j, i) = (0,0), (0,1), (1,0), (1,1) in this order,
+ *                   k = (i ? ax : 1.f - ax) * (j ? ay : 1.f - ay)
+ *       for each tap:  q = (x0 + i, y0 + j)
+ *         skip unless 0 <= q.w <= W-1 and 0 <= q.h <= H-1       (compared as floats BEFORE any conversion to int)
+ *         skip unless k > 0                                                                 -> taps_tested += 1
+ *         skip unless hit_prev(q)
+ *         skip unless history_n[q] >= 1
+ *         skip if same_object and !(geom_prev[q] == geom_cur[p] && (geom_cur[p] >= 0 || prim_prev[q] == prim_cur[p]))
+ *         skip unless dot(N_p, Nprev_q) >= normal_cos
+ *         skip unless fabsf(dot(Pprev_q - P_p, N_p)) <= plane_dist                          -> taps_accepted += 1
+ *         acc_c = fl(acc_c + fl(k * history[q]_c));   ws = fl(ws + k);   n = min(n, history_n[q])
+ *     if !(ws > 0):  out[p] = current[p];  out_n[p] = 1
+ *     else:                                                                                 -> reused_pixels += 1
+ *       m = min(n, M - 1) + 1;   alpha = 1.f / float(m)
+ *       hc = fl(acc_c / ws);     out[p]_c = fl(hc + fl(fl(current[p]_c - hc) * alpha));   out_n[p] = m
+ *
+ * What follows from it:
+ *   - A first frame is this call with d_history_n all zero: every tap is refused, the output is current, and
+ *     n = 1 on hits.
+ *   - A pixel's n is the smallest n among its accepted taps, plus one, capped at M.  Up to M the value is the
+ *     running mean; from M on it is an exponential average with alpha = 1/M.
+ *   - Pixels without a hit carry no history (n = 0).
+ *   - The scene is assumed static between the two frames, because positions are compared in world space.  The
+ *     object, normal and plane stops are what reject disocclusions; nothing detects a moved object.
+ *   - A comparison with a NaN is false: a NaN position or camera makes the pixel not valid, a NaN guide skips
+ *     the tap.  A NaN or infinite history or current value spreads to the pixels that accept it, as written.
+ *
+ * d_out must not be d_history and d_out_n must not be d_history_n (ESC_ERR_INVALID each), because taps read
+ * neighbours; d_out may be d_current.  ESC_ERR_INVALID also: W or H < 2, channels other than 1 or 3, taps
+ * other than 1 or 4, max_history outside 1..65536, a NaN threshold, a negative plane_dist, same_object other
+ * than 0 / 1, a non-zero reserved, a null or misaligned (4 bytes) pointer.  The call is asynchronous on the
+ * context's stream with no host synchronisation, needs no scene and no scratch; the stats counters are device
+ * words the context owns and frees.
+ * Out of scope: motion vectors for moving objects, variance or moment buffers, colour-box clamping, albedo
+ * demodulation, reprojecting specular or traced colour. */
+typedef struct esc_guides {          /* four arrays as esc_render_gbuffer writes them, W*H pixels, DEVICE pointers */
+  const float *normal;               /* W*H x 3 */
+  const float *position;             /* W*H x 3 */
+  const int32_t *geom, *prim;        /* W*H each */
+} esc_guides;
+typedef struct esc_temporal_options {
+  int32_t taps;         /* 1: the nearest history pixel; 4: bilinear over the 2 x 2 around the reprojected point */
+  int32_t max_history;  /* M, 1..65536: the history length saturates at M (alpha never below 1/M) */
+  float normal_cos;     /* as esc_filter_options; not NaN */
+  float plane_dist;     /* as esc_filter_options; >= 0, not NaN; FLT_MAX or inf: off */
+  int32_t same_object;  /* 0 / 1 */
+  int32_t reserved[3];  /* 0 */
+} esc_temporal_options;
+typedef struct esc_temporal_stats {
+  uint64_t pixels;        /* W*H */
+  uint64_t hit_pixels;    /* pixels with hit_cur(p): the others are copied */
+  uint64_t reused_pixels; /* hit pixels that accepted at least one history tap (ws > 0) */
+  uint64_t taps_tested;   /* taps inside the previous image with k > 0 */
+  uint64_t taps_accepted; /* ... that passed every stop */
+} esc_temporal_stats;
+int esc_temporal_accumulate(esc_context *ctx, const esc_camera *prev_cam, int32_t W, int32_t H, int32_t channels,
+                            const float *d_current, const esc_guides *cur,
+                            const float *d_history, const int32_t *d_history_n, const esc_guides *prev,
+                            const esc_temporal_options *opts, float *d_out, int32_t *d_out_n);
+/* counts of the last esc_temporal_accumulate call (zero before the first); synchronises the stream */
+int esc_last_temporal_stats(esc_context *ctx, esc_temporal_stats *out);
 
 /* ---- environment cube map: traced rays that miss see a sky (rt_environ.h, rt_environ.hip, rt_trace.hip,
  * DESIGN.md section 3.18) ----
