@@ -1210,6 +1210,20 @@ class Renderer:
         -> (int32 array of the stored entries, at most the global capacity; the appended count)"""
         return self.tile_list_ids(which, -1)
 
+    def tile_tri_masks(self):
+        """esc_tile_tri_masks: the per-tile triangle masks of the last frame (a directly swept table of 1
+        to 32 triangles) -> dict "off" (the masks switched themselves off), "global" (the word every tile
+        ORs in), "tiles_x", "tile_rows", "n_tri", "masks" (tile_rows, tiles_x) uint32 -- or None when the
+        frame had none"""
+        info = (C.c_int32 * 8)()
+        n = check(self._lib.esc_tile_tri_masks(self._h, info, None, 0))
+        if n == 0:
+            return None
+        m = np.zeros(n, np.uint32)
+        check(self._lib.esc_tile_tri_masks(self._h, info, m.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return {"off": info[0], "global": int(info[1]) & 0xFFFFFFFF, "tiles_x": info[2], "tile_rows": info[3],
+                "n_tri": info[4], "masks": m.reshape(info[3], info[2])}
+
     def light_lists(self, which):
         """esc_light_list_read: the light lists of the last frame (which = 2 sphere pair records, 3 triangle
         pair records) as numpy arrays, or None when the frame used none -> dict: "n_listed", "R", "cap",

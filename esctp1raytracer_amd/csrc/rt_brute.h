@@ -77,6 +77,40 @@ DEVINL void test_tri2_primary(const DevTriP (&T)[2], int idx, const V3<V> (&d)[N
   }
 }
 
+// ONE triangle: the statements of one slot of test_tri2_primary, nothing else -- no second slot, no
+// filter.  For the callers that know which triangles a wave needs at all (the per-tile masks of
+// rt_lists.h): in ascending index order it is closest_tri_primary with the unneeded passes left out.
+template <typename V, int NV>
+DEVINL void test_tri_primary(const DevTriP &T, int idx, const V3<V> (&d)[NV], Hit (&h)[NV * lanes_of<V>::n]) {
+  constexpr int LN = lanes_of<V>::n;
+  V det[NV], un[NV], vn[NV];
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const V3<V> pv = cross_vu(d[j], ld3(T.e2)); // ray_triangle.h:18
+    det[j] = dotu(ld3(T.e1), pv);               // :21
+    un[j] = dotu(ld3(T.tv), pv);                // :32 numerator
+    vn[j] = dotu(ld3(T.qv), d[j]);              // :40 numerator
+#pragma unroll
+    for (int c = 0; c < LN; ++c) any |= tri_candidate(comp(det[j], c), comp(un[j], c), comp(vn[j], c));
+  }
+  if (ANY_LANE_RARE(any)) { // wave-uniform skip of the f64 tail
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+#pragma unroll
+      for (int c = 0; c < LN; ++c) {
+        Hit &hh = h[j * LN + c];
+        const float de = comp(det[j], c), u = comp(un[j], c), v = comp(vn[j], c);
+        float t2, v2;
+        if (tri_candidate(de, u, v) && tri_exact(de, u, v, T.tnum, hh.t, t2, v2)) {
+          hh.t = t2;
+          hh.v = v2;
+          hh.idx = idx;
+        }
+      }
+  }
+}
+
 template <typename V, int NV, typename Fetch>
 DEVINL void closest_tri_primary(Fetch rec, int n, int base, const V3<V> (&d)[NV],
                                 Hit (&h)[NV * lanes_of<V>::n]) {

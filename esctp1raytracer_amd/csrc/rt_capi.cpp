@@ -156,8 +156,10 @@ struct esc_context {
   struct ListKey {
     float cam[12];
     int32_t W, H, h0, n_local_rows, strip_rows, strip_step, n_sg, n_tg;
+    int32_t n_mask_tri; // > 0: tl.cnt holds the triangle masks of that many directly swept triangles
   } list_key{};
   bool lists_valid = false;
+  bool tri_masks_last = false; // the last frame asked for the masks (and list_key describes them)
   bool list_ids_stale = false; // a new scene: ids of the old one may be out of range
   // light lists of the shadow pass (rt_device.h LightLists), valid for (scene, ll_face_mode, ll_fixed_face)
   esc::LightLists ll{}, lt{}; // sphere / triangle pair records
@@ -896,6 +898,7 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
   p.sph2 = ctx->d_sph2;
   p.sph_f = ctx->d_sph_f;
   p.sph2_f = ctx->d_sph2_f;
+  bool linear_sweeps = false; // ESC_RENDER_INDEX_ORDER / ESC_GROUPS=0: the linear loops, untouched by any list
   {
     static const bool env_index = [] {
       const char *e = std::getenv("ESC_ORDER");
@@ -912,6 +915,7 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
     p.tg = ctx->tg;
     if (index_order || env_nogroups)
       p.sg.n_grp = p.sg.n_sup = p.sg.n_hyp = p.tg.n_grp = p.tg.n_sup = p.tg.n_hyp = 0;
+    linear_sweeps = index_order || env_nogroups;
 
   }
   p.tri_f = ctx->d_tri_f;
@@ -992,9 +996,15 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
       const char *e = std::getenv("ESC_LISTS");
       return e && std::strcmp(e, "0") == 0;
     }();
-    const bool want = !env_nolists && !(opts->flags & ESC_RENDER_NO_TILE_LISTS) && p.use_filter &&
-                      (p.sg.n_grp > 0 || p.tg.n_grp > 0) && eff_stage != ESC_STAGE_LDS &&
-                      eff_stage != ESC_STAGE_BVH && (h0 % 4) == 0;
+    const bool allowed = !env_nolists && !(opts->flags & ESC_RENDER_NO_TILE_LISTS) && p.use_filter &&
+                         eff_stage != ESC_STAGE_LDS && eff_stage != ESC_STAGE_BVH && (h0 % 4) == 0;
+    // a triangle table too small for groups, swept directly: one mask word per tile in tl.cnt instead
+    // (rt_lists.h "Per-tile triangle masks"); switched with the lists.  Only the kernels with two pixels
+    // per lane read them (primary_closest, PX == 2): a frame of 1 or 4 pixels per lane builds none.
+    const bool px2 = opts->pixels_per_lane == 0 || opts->pixels_per_lane == 2;
+    const bool want_masks = allowed && px2 && !linear_sweeps && p.n_tri > 0 && p.n_tri <= 32;
+    const bool want = allowed && (p.sg.n_grp > 0 || p.tg.n_grp > 0 || want_masks);
+    ctx->tri_masks_last = want_masks;
     if (want) {
       const int tiles_x = (W + 31) / 32, tile_rows = (n_local_rows + 3) / 4;
       const size_t n_tiles = (size_t)tiles_x * tile_rows;
@@ -1035,12 +1045,15 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
       key.W = W; key.H = H; key.h0 = h0; key.n_local_rows = n_local_rows;
       key.strip_rows = strip_rows; key.strip_step = strip_step;
       key.n_sg = p.sg.n_grp; key.n_tg = p.tg.n_grp;
+      key.n_mask_tri = want_masks ? p.n_tri : 0;
       p.sl = ctx->sl;
       p.tl = ctx->tl;
       p.sl.tiles_x = p.tl.tiles_x = tiles_x;
       p.sl.tile_rows = p.tl.tile_rows = tile_rows;
       p.sl.enabled = p.sg.n_grp > 0;
       p.tl.enabled = p.tg.n_grp > 0;
+      p.sl.masks = 0;
+      p.tl.masks = want_masks ? 1 : 0;
       if (!ctx->lists_valid || std::memcmp(&key, &ctx->list_key, sizeof(key)) != 0) {
         for (const esc::TileLists *L : {&p.sl, &p.tl}) {
           HIP_TRY(hipMemsetAsync(L->hdr, 0, (size_t)esc::kTileHdrInts * 4, ctx->stream));
@@ -1598,6 +1611,25 @@ int esc_tile_list_ids(esc_context *ctx, int32_t which, int64_t index, int32_t *i
   const int m = std::min(std::min(c, cap), capacity);
   if (m > 0) HIP_TRY(hipMemcpy(ids, d_ids + index * cap, (size_t)m * 4, hipMemcpyDeviceToHost));
   return c;
+}
+
+int esc_tile_tri_masks(esc_context *ctx, int32_t info[8], uint32_t *masks, size_t capacity) {
+  if (!ctx || !info) {
+    set_error("esc_tile_tri_masks: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  const esc::TileLists &L = ctx->tl;
+  if (!ctx->tri_masks_last || !ctx->lists_valid || !L.hdr || !L.cnt || ctx->list_key.n_mask_tri <= 0) return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  int32_t h[5];
+  HIP_TRY(hipMemcpy(h, L.hdr, sizeof(h), hipMemcpyDeviceToHost));
+  const int tiles_x = (ctx->list_key.W + 31) / 32, tile_rows = (ctx->list_key.n_local_rows + 3) / 4;
+  const int32_t out[8] = {h[2], h[4], tiles_x, tile_rows, ctx->list_key.n_mask_tri, 0, 0, 0};
+  std::memcpy(info, out, sizeof(out));
+  const size_t n_tiles = (size_t)tiles_x * tile_rows;
+  if (masks) HIP_TRY(hipMemcpy(masks, L.cnt, std::min(capacity, n_tiles) * 4, hipMemcpyDeviceToHost));
+  return (int)n_tiles;
 }
 
 int esc_light_list_read(esc_context *ctx, int32_t which, int32_t info[8], int32_t *face_counts,

@@ -300,7 +300,8 @@ struct TileLists {
   int32_t tiles_x;   // ceil(W / 32)
   int32_t tile_rows; // ceil(n_local_rows / 4)
   int32_t enabled;   // 0: no lists (the sweep over the levels)
-  int32_t pad;
+  int32_t masks;     // tl only, 1: cnt[] holds per-tile triangle MASKS of an ungrouped table of at most 32
+                     // triangles, hdr[4] the global word (rt_lists.h "Per-tile triangle masks")
 };
 
 // ---------------------------------------------------------------------------------------

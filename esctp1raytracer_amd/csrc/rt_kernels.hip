@@ -641,6 +641,18 @@ DEVINL void primary_closest(const RenderParams &p, const Tile<PX> &T, const V3<V
               SmemFetch<TriPF>{reinterpret_cast<const TriPF *>(p.tg.grp_pf) + p.tg.n_grp},
               SmemFetch<TriPF>{reinterpret_cast<const TriPF *>(p.tg.grp_pf)}, recp, recf, rece, reci,
               p.tg.n_hyp, dv[0], hit);
+      } else if (p.tl.masks && ((ListPtr)(uintptr_t)p.tl.hdr)[2] == 0) {
+        // a small table with per-tile masks (rt_lists.h "Per-tile triangle masks"): only the triangles
+        // this tile's rays can be accepted by, in index order, through the reference arithmetic
+        uint32_t m = 0;
+        if (tile_ok)
+          m = (uint32_t)(((ListPtr)(uintptr_t)p.tl.cnt)[tile] | ((ListPtr)(uintptr_t)p.tl.hdr)[4]);
+        const SmemFetch<DevTriP> rec{p.tri_p};
+        while (m) {
+          const int k = __builtin_ctz(m);
+          m &= m - 1;
+          test_tri_primary<V, NV>(rec(k), k, dv, hit);
+        }
       } else {
       const int n2 = (p.use_filter && p.n_tri >= 8) ? (p.n_tri & ~3) : 0;
       closest_tri_primary_filter(SmemFetch<TriPF>{reinterpret_cast<const TriPF *>(p.tri_pf)},
@@ -1952,6 +1964,13 @@ extern "C" int esc_launch_tile_lists(const esc::RenderParams *p, hipStream_t str
   if (p->tl.enabled && p->tg.n_grp > 0) {
     hipLaunchKernelGGL(esc::k_bin_triangles, dim3(p->tg.n_grp * esc::kTriGroup / 4), dim3(256), 0, stream, *p);
     hipLaunchKernelGGL(esc::k_bin_tri_escape, dim3((unsigned)p->tl.tile_rows), dim3(256), 0, stream, *p);
+  }
+  if (p->tl.masks && p->n_tri > 0 && p->n_tri <= 32) {
+    // a triangle's tiles shared out over enough workgroups that a wave takes about 16 of them in turn
+    const long long n_tiles = (long long)p->tl.tiles_x * p->tl.tile_rows;
+    const long long want = n_tiles / (256 * 16);
+    const unsigned parts = (unsigned)(want < 1 ? 1 : want > 64 ? 64 : want);
+    hipLaunchKernelGGL(esc::k_bin_tri_masks, dim3((unsigned)p->n_tri, parts), dim3(256), 0, stream, *p);
   }
   return (int)hipGetLastError();
 }

@@ -61,27 +61,55 @@
 
 namespace esc {
 
-DEVINL void list_global(const TileLists &L, int id) {
-  const int slot = atomicAdd(&L.hdr[0], 1);
-  if (slot < kTileGlobalCap) L.hdr[8 + slot] = id;
-}
+// Where a binning kernel puts its answers.  The rule that finds a primitive's tiles (bin_triangle, the
+// rectangles below) is written once against a SINK; the two sinks differ only in how a tile remembers:
+//   TileListSink  the lists above: an id appended per tile (hdr[0] / hdr[8..): the global list);
+//   TileMaskSink  "Per-tile triangle masks" below: bit `id` of the tile's word in cnt[] (hdr[4]: the
+//                 global word every tile ORs in).  Setting a bit twice is setting it once, so the
+//                 tiles of one triangle may be shared out over `parts` waves; it has no use for cone
+//                 entries (kEscEntries) and no cost that grows with the span (kMaxSpan).
+struct TileListSink {
+  TileLists L;
+  static constexpr bool kEscEntries = true;
+  static constexpr long long kMaxSpan = kTileMaxSpan;
+  DEVINL int part() const { return 0; }
+  DEVINL int parts() const { return 1; }
+  DEVINL void off() const { L.hdr[2] = 1; }
+  DEVINL void global(int id) const {
+    const int slot = atomicAdd(&L.hdr[0], 1);
+    if (slot < kTileGlobalCap) L.hdr[8 + slot] = id;
+  }
+  DEVINL void tile(int tile, int id) const {
+    const int slot = atomicAdd(&L.cnt[tile], 1);
+    if (slot < kTileListCap) L.ids[(size_t)tile * kTileListCap + slot] = id;
+  }
+};
+struct TileMaskSink {
+  TileLists L;
+  int part_, parts_;
+  static constexpr bool kEscEntries = false;
+  static constexpr long long kMaxSpan = 0x7fffffffll;
+  DEVINL int part() const { return part_; }
+  DEVINL int parts() const { return parts_; }
+  DEVINL void off() const { L.hdr[2] = 1; }
+  DEVINL void global(int id) const { atomicOr(&L.hdr[4], (int)(1u << id)); }
+  DEVINL void tile(int tile, int id) const { atomicOr(&L.cnt[tile], (int)(1u << id)); }
+};
 
 // append `id` to every tile of the band that the pixel rectangle overlaps, the wave side by side;
 // global when the rectangle spans very many tiles
-DEVINL void list_rect(const RenderParams &p, const TileLists &L, int w0, int w1, int h0, int h1, int id,
-                      int lane) {
+template <typename Sink>
+DEVINL void list_rect(const RenderParams &p, const Sink &S, int w0, int w1, int h0, int h1, int id, int lane) {
   const int tx0 = w0 >> 5, tx1 = w1 >> 5, j0 = h0 >> 2, j1 = h1 >> 2;
-  if ((long long)(tx1 - tx0 + 1) * (j1 - j0 + 1) > kTileMaxSpan) {
-    if (lane == 0) list_global(L, id);
+  if ((long long)(tx1 - tx0 + 1) * (j1 - j0 + 1) > Sink::kMaxSpan) {
+    if (lane == 0) S.global(id);
     return;
   }
   const int nx = tx1 - tx0 + 1, n = nx * (j1 - j0 + 1);
-  for (int k = lane; k < n; k += 64) {
+  for (int k = lane + 64 * S.part(); k < n; k += 64 * S.parts()) {
     const int r4 = band_tile_row(p, j0 + k / nx);
     if (r4 < 0) continue;
-    const int tile = r4 * L.tiles_x + tx0 + k % nx;
-    const int slot = atomicAdd(&L.cnt[tile], 1);
-    if (slot < kTileListCap) L.ids[(size_t)tile * kTileListCap + slot] = id;
+    S.tile(r4 * S.L.tiles_x + tx0 + k % nx, id);
   }
 }
 
@@ -93,15 +121,16 @@ DEVINL void list_rect(const RenderParams &p, const TileLists &L, int w0, int w1,
 struct HullAxes {
   double nx[3], ny[3], lo[3], hi[3];
 };
-DEVINL void list_rect_hull(const RenderParams &p, const TileLists &L, int w0, int w1, int h0, int h1, int id,
+template <typename Sink>
+DEVINL void list_rect_hull(const RenderParams &p, const Sink &S, int w0, int w1, int h0, int h1, int id,
                            int lane, const HullAxes &A) {
   const int tx0 = w0 >> 5, tx1 = w1 >> 5, j0 = h0 >> 2, j1 = h1 >> 2;
-  if ((long long)(tx1 - tx0 + 1) * (j1 - j0 + 1) > kTileMaxSpan) {
-    if (lane == 0) list_global(L, id);
+  if ((long long)(tx1 - tx0 + 1) * (j1 - j0 + 1) > Sink::kMaxSpan) {
+    if (lane == 0) S.global(id);
     return;
   }
   const int nx = tx1 - tx0 + 1, n = nx * (j1 - j0 + 1);
-  for (int k = lane; k < n; k += 64) {
+  for (int k = lane + 64 * S.part(); k < n; k += 64 * S.parts()) {
     const int j = j0 + k / nx, tx = tx0 + k % nx;
     const int r4 = band_tile_row(p, j);
     if (r4 < 0) continue;
@@ -114,9 +143,7 @@ DEVINL void list_rect_hull(const RenderParams &p, const TileLists &L, int w0, in
       outside |= (tmax < A.lo[a]) | (tmin > A.hi[a]);
     }
     if (outside) continue;
-    const int tile = r4 * L.tiles_x + tx;
-    const int slot = atomicAdd(&L.cnt[tile], 1);
-    if (slot < kTileListCap) L.ids[(size_t)tile * kTileListCap + slot] = id;
+    S.tile(r4 * S.L.tiles_x + tx, id);
   }
 }
 
@@ -127,10 +154,10 @@ __global__ void __launch_bounds__(256) k_bin_spheres(const RenderParams p) {
   if (s >= p.sg.n_grp * kSphGroup) return;
   const DevSph S = p.sg.sorted[s];
   if (!(S.r2 >= 0.f)) return; // pad slot (r2 = -inf): never hit
-  const TileLists L = p.sl;
+  const TileListSink L{p.sl};
   const CamD cam = cam_frame(p);
   if (!cam.ok) {
-    if (lane == 0) L.hdr[2] = 1;
+    if (lane == 0) L.off();
     return;
   }
   const double c[3] = {(double)S.cx - cam.o[0], (double)S.cy - cam.o[1], (double)S.cz - cam.o[2]};
@@ -141,7 +168,7 @@ __global__ void __launch_bounds__(256) k_bin_spheres(const RenderParams p) {
   const int st = sphere_pixel_rect(cam, p.W, p.H, c, R, w0, w1, h0, h1);
   if (st == 2) return; // off screen
   if (st == 0) {
-    if (lane == 0) list_global(L, s);
+    if (lane == 0) L.global(s);
     return;
   }
   list_rect(p, L, w0, w1, h0, h1, s, lane);
@@ -214,19 +241,17 @@ DEVINL TriEscape tri_escape(const DevTri &T, f3 o, float slack_k) {
 }
 
 
-// one wave per slot of the group-sorted triangle table: global / (S_t) rectangle / (E_t) cone entry
-__global__ void __launch_bounds__(256) k_bin_triangles(const RenderParams p) {
-  const int k = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-  const int lane = (int)(threadIdx.x & 63u);
-  if (k >= p.tg.n_grp * kTriGroup) return;
-  const DevTri T = p.tg.sorted[k];
+// The rule for ONE triangle, a wave per call: global / (S_t) rectangle / (E_t) cone entry, told to the
+// sink under the name `k`.  k_bin_triangles runs it over the slots of the group-sorted table and
+// k_bin_tri_masks over the triangles of a small table in index order: one rule, two memories.  A sink
+// without cone entries (the masks) takes a triangle whose escape this camera can reach as global.
+template <typename Sink> DEVINL void bin_triangle(const RenderParams &p, const DevTri &T, int k, int lane, const Sink &L) {
   const f3 e1f = ld3(T.e1), e2f = ld3(T.e2);
   if (e1f.x == 0.f && e1f.y == 0.f && e1f.z == 0.f && e2f.x == 0.f && e2f.y == 0.f && e2f.z == 0.f)
     return; // pad slot (or a point): det == 0 exactly, never accepted
-  const TileLists L = p.tl;
   const CamD cam = cam_frame(p);
   if (!cam.ok) {
-    if (lane == 0) L.hdr[2] = 1;
+    if (lane == 0) L.off();
     return;
   }
   const double e1[3] = {e1f.x, e1f.y, e1f.z}, e2[3] = {e2f.x, e2f.y, e2f.z};
@@ -242,8 +267,8 @@ __global__ void __launch_bounds__(256) k_bin_triangles(const RenderParams p) {
   const TriEscape E = tri_escape(T, mk(p.origin[0], p.origin[1], p.origin[2]), 1.f);
   const bool sliver = !(rho > 0x1.4p-10 * emax) || !(nn > 0.0) || !(l1 > 0.0); // (the pre-filter's own
                                                                                 // threshold is 2^-10)
-  if (sliver || (E.possible && !E.bounded)) { // passed on for every ray
-    if (lane == 0) list_global(L, k);
+  if (sliver || (E.possible && (!E.bounded || !Sink::kEscEntries))) { // passed on for every ray
+    if (lane == 0) L.global(k);
     return;
   }
   // Statement (K) of rt_brute.h trades the two halves (as the triangle light lists do per light): with
@@ -264,8 +289,8 @@ __global__ void __launch_bounds__(256) k_bin_triangles(const RenderParams p) {
       }
     }
   }
-  if (E.possible && lane == 0) { // the camera is nearly in this plane: k_bin_tri_escape bins the band
-    const int slot = atomicAdd(&L.hdr[1], 1);
+  if (Sink::kEscEntries && E.possible && lane == 0) { // the camera is nearly in this plane: k_bin_tri_escape bins the band
+    const int slot = atomicAdd(&L.L.hdr[1], 1);
     if (slot < kTileEscCap) {
       TileEsc X;
       const double nh[3] = {E.nh.x, E.nh.y, E.nh.z};
@@ -307,7 +332,7 @@ __global__ void __launch_bounds__(256) k_bin_triangles(const RenderParams p) {
       X.vV = use_v ? dot3(V, mv) / lv : 0.0;
       X.kpv = use_v ? (float)(kv * (1.0 + 0x1p-20)) : 2.f;
       X.pad[0] = X.pad[1] = 0;
-      L.esc[slot] = X;
+      L.L.esc[slot] = X;
     }
   }
   // (S_t): lanes 0..11 take the corners v_i +- rho' e_a +- rho' e_b
@@ -330,7 +355,7 @@ __global__ void __launch_bounds__(256) k_bin_triangles(const RenderParams p) {
   // says nothing (the triangle's image runs through infinity)
   const unsigned long long front = __builtin_amdgcn_ballot_w64(depth > 0.0);
   if (__builtin_amdgcn_ballot_w64(!bounded) != 0 || (front != 0 && front != ~0ull)) {
-    if (lane == 0) list_global(L, k);
+    if (lane == 0) L.global(k);
     return;
   }
   // An extent at the clamp of sphere_pixel_extent (+-1e9 px): clamping moves a far corner coordinate by
@@ -376,6 +401,33 @@ __global__ void __launch_bounds__(256) k_bin_triangles(const RenderParams p) {
     return;
   }
   list_rect_hull(p, L, w0, w1, h0, h1, k, lane, HA);
+}
+
+// one wave per slot of the group-sorted triangle table
+__global__ void __launch_bounds__(256) k_bin_triangles(const RenderParams p) {
+  const int k = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  const int lane = (int)(threadIdx.x & 63u);
+  if (k >= p.tg.n_grp * kTriGroup) return;
+  bin_triangle(p, p.tg.sorted[k], k, lane, TileListSink{p.tl});
+}
+
+// Per-tile triangle masks.  A table of fewer than kTriGroupMinTris triangles has no groups and no
+// lists: every wave of the primary pass tests every triangle of p.tri directly.  For 0 < n_tri <= 32
+// the same question the lists answer -- what can this tile's rays touch -- fits one 32-bit word per
+// tile: bit k of tl.cnt[tile] set <=> bin_triangle put triangle k of p.tri (its ORIGINAL index) into
+// the tile; tl.hdr[4] is the word of the global triangles, which every tile ORs in; tl.hdr[2] != 0:
+// nothing can be said (a singular camera frame), test them all.  Soundness is the statement at the
+// top, which speaks of the reference's own accept: the consumer (primary_closest) runs the reference
+// arithmetic on the set bits in ascending order with no filter in front of it, so a clear bit only
+// ever removes a test that this tile's rays cannot pass.  An (E_t) escape the camera can reach makes
+// the triangle global here: with at most 32 triangles a cone entry would save nothing worth its code.
+// blockIdx.x: the triangle; the 4 waves of the gridDim.y workgroups share its tiles out.
+__global__ void __launch_bounds__(256) k_bin_tri_masks(const RenderParams p) {
+  const int k = (int)blockIdx.x;
+  const int lane = (int)(threadIdx.x & 63u);
+  if (k >= p.n_tri || k >= 32) return;
+  const TileMaskSink S{p.tl, (int)(blockIdx.y * 4 + (threadIdx.x >> 6)), (int)gridDim.y * 4};
+  bin_triangle(p, p.tri[k], k, lane, S);
 }
 
 // (E_t): one workgroup per tile row: p . n = fA + s fH + t fV is affine, so over the row's t range the band

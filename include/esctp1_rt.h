@@ -551,6 +551,18 @@ int esc_tile_list_counts(esc_context *ctx, int32_t which, int32_t hdr[8], int32_
  * (2, 3) keep one global list per face and have no such call: index = -1 is ESC_ERR_INVALID there. */
 int esc_tile_list_ids(esc_context *ctx, int32_t which, int64_t index, int32_t *ids, int32_t capacity);
 
+/* The per-tile triangle masks of the last frame, for inspection and tests; read-only.  A scene whose
+ * triangle table is swept directly (no groups, so esc_tile_list_counts(which = 1) reports no lists) and
+ * holds 1 to 32 triangles gets one 32-bit word per 32 x 4 pixel tile of the band: bit k set means some
+ * primary ray of the tile may be accepted by triangle k (original index).  info receives {state, global
+ * word, tiles per row, tile rows, triangles, 0, 0, 0}: state != 0 -- the masks switched themselves off for
+ * this camera and every tile tests every triangle; the global word's triangles are tested by every tile.
+ * Up to `capacity` words are copied to `masks` (may be NULL), tiles in the order of esc_tile_list_counts.
+ * Returns the number of tiles, 0 when the last frame had no masks (more than 32 triangles or none, a
+ * grouped table, a band that does not start on a multiple of 4 rows, pixels_per_lane 1 or 4,
+ * ESC_RENDER_NO_TILE_LISTS and the other paths that take no lists), or a negative error.  Synchronises the context's stream. */
+int esc_tile_tri_masks(esc_context *ctx, int32_t info[8], uint32_t *masks, size_t capacity);
+
 /* ... and the light lists (which = 2 sphere pair records, 3 triangle pair records) as a whole, for
  * inspection and tests; read-only.  info receives {lights with lists, cells per face side R, list
  * capacity, global capacity, point[0..3]}: point[li] is the row of the light_points table the lists of
