@@ -358,22 +358,10 @@ class Renderer:
                     stage=ESC_STAGE_AUTO, px=0, flags=0):
         """Asynchronous band render into DEVICE buffers (torch tensors or raw pointers),
         band-local layout ((h - row_begin) * W + w) * 3."""
-        n = (row_end - row_begin) * W * 3
-
-        def ptr(buf, itemsize):
-            if buf is None:
-                return None
-            if hasattr(buf, "data_ptr"):
-                if buf.numel() * buf.element_size() < n * itemsize:
-                    raise ValueError("output buffer too small for the band")
-                if not buf.is_cuda or not buf.is_contiguous():
-                    raise ValueError("output must be a contiguous device tensor")
-                return C.c_void_p(buf.data_ptr())
-            return C.c_void_p(int(buf))
-
+        n = max(0, row_end - row_begin) * W * 3
         o = _options(shadows, face_mode, fixed_face, seed, stage, px, flags)
         check(self._lib.esc_render_rows(self._h, C.byref(camera.c), W, H, row_begin, row_end,
-                                        C.byref(o), ptr(out_f32, 4), ptr(out_u8, 1)))
+                                        C.byref(o), self._dev_ptr(out_f32, n * 4), self._dev_ptr(out_u8, n)))
 
     @staticmethod
     def _dev_ptr(buf, nbytes):
@@ -418,8 +406,16 @@ class Renderer:
     def assemble_strips(self, gathered, n_ranks, rank_pitch_bytes, W, H, frame, *, strip_rows=8,
                         bytes_per_pixel=12):
         """gathered: n_ranks blocks of local rows (block r at r*rank_pitch_bytes) -> frame."""
+        need = 0  # the end of the last local row the kernel reads, over the ranks
+        if hasattr(gathered, "data_ptr") and n_ranks >= 1 and strip_rows >= 1:
+            n_strips = (H + strip_rows - 1) // strip_rows
+            for r in range(min(n_ranks, n_strips)):
+                rows = (n_strips - r + n_ranks - 1) // n_ranks * strip_rows
+                if (n_strips - 1) % n_ranks == r:  # the image's last strip may be short
+                    rows -= n_strips * strip_rows - H
+                need = max(need, r * rank_pitch_bytes + rows * W * bytes_per_pixel)
         check(self._lib.esc_assemble_strips(
-            self._h, self._dev_ptr(gathered, 0), n_ranks, rank_pitch_bytes, W, H, strip_rows,
+            self._h, self._dev_ptr(gathered, need), n_ranks, rank_pitch_bytes, W, H, strip_rows,
             bytes_per_pixel, self._dev_ptr(frame, W * H * bytes_per_pixel)))
 
     def render(self, camera, W, H, *, want_u8=False, shadows=True, face_mode=ESC_FACE_FIXED,

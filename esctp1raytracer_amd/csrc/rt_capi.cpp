@@ -860,6 +860,11 @@ int render_local_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
       set_error("render: camera is not finite (lookfrom == lookat, or a zero / NaN aspect?)");
       return ESC_ERR_INVALID;
     }
+  // the kernels store d_rgb_f32 as floats; d_rgb_u8 is written byte by byte unless it is aligned itself
+  if (((uintptr_t)d_rgb_f32) & 3u) {
+    set_error("render: device pointers must be 4-byte aligned (d_rgb_u8 excepted)");
+    return ESC_ERR_INVALID;
+  }
   if (n_local_rows == 0) return ESC_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   // ESC_STAGE_BVH culls with proven bounds only.  Its tree and bins are proven for spheres (box pads
@@ -1467,6 +1472,11 @@ int esc_assemble_strips(esc_context *ctx, const void *d_gathered, int32_t n_rank
   if (!ctx || !d_gathered || !d_frame || n_ranks < 1 || W < 1 || H < 1 || strip_rows < 1 ||
       bytes_per_pixel < 1) {
     set_error("esc_assemble_strips: bad argument");
+    return ESC_ERR_INVALID;
+  }
+  // fp32 pixels (any pixel size that is a multiple of 4 bytes) are floats to whoever reads the frame
+  if (bytes_per_pixel % 4 == 0 && ((((uintptr_t)d_gathered) | ((uintptr_t)d_frame)) & 3u)) {
+    set_error("esc_assemble_strips: device pointers must be 4-byte aligned (byte pixels excepted)");
     return ESC_ERR_INVALID;
   }
   HIP_TRY(hipSetDevice(ctx->device));

@@ -534,7 +534,9 @@ DEVINL void write_tile(const RenderParams &p, const Tile<1> &T, int tid, float r
     const float cr = (r > 1.f) ? 1.f : r, cg = (g > 1.f) ? 1.f : g, cb = (b > 1.f) ? 1.f : b;
     const uint8_t qr = (uint8_t)(int)(cr * 255.f), qg = (uint8_t)(int)(cg * 255.f),
                   qb = (uint8_t)(int)(cb * 255.f);
-    if (full_tile && (p.W & 3) == 0) {
+    // dword stores need a 4-byte aligned address: rows are then W * 3 = 0 (mod 4) bytes apart and w0 * 3
+    // is a multiple of 96, so it is the caller's pointer that decides (d_rgb_u8 may have any alignment)
+    if (full_tile && (p.W & 3) == 0 && (reinterpret_cast<uintptr_t>(p.out_u8) & 3) == 0) {
       __syncthreads(); // lds_px reuse
       unsigned char *lb = reinterpret_cast<unsigned char *>(lds_px);
       const int li = (ly * TW + lx) * 3;

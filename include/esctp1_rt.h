@@ -383,6 +383,10 @@ int esc_check_flat(int32_t num_triangles, const ispc_triangle *triangles, int32_
  * stream.  Outputs are DEVICE pointers, band-local: pixel (w,h) at ((h-row_begin)*W+w)*3.
  *   d_rgb_f32  fp32 RGB accumulators (may be NULL)
  *   d_rgb_u8   8-bit RGB after the PPM clamp/truncate of main.cpp:676-682 (may be NULL)
+ * Device pointers must be 4-byte aligned (d_rgb_u8 excepted: any address); a misaligned d_rgb_f32 is
+ * ESC_ERR_INVALID and nothing is launched.  Exactly the band's (row_end - row_begin) * W * 3 elements
+ * of each non-NULL output are written, every pixel of the band, misses (0, 0, 0) included, and nothing
+ * else; an empty band writes nothing.
  * Counters accumulate on the device; read them with esc_read_counters (synchronises). */
 int esc_render_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
                     int32_t row_begin, int32_t row_end, const esc_render_options *opts,
@@ -392,7 +396,9 @@ int esc_render_rows(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t 
  * renders strips first_strip, first_strip + strip_stride, ... -- i.e. rank r of N calls it
  * with (first_strip = r, strip_stride = N).  Dealing strips round-robin balances sky rows
  * (primary rays only) against floor rows (primary + shadow).  strip_rows must be a multiple of
- * 8.  Output: the rendered rows packed in ascending h, esc_strip_local_rows() of them. */
+ * 8.  Output: the rendered rows packed in ascending h, esc_strip_local_rows() of them: exactly those
+ * rows * W * 3 elements of each non-NULL output are written (none when the rank has no strip).
+ * Alignment as for esc_render_rows: d_rgb_f32 4-byte aligned or ESC_ERR_INVALID, d_rgb_u8 anywhere. */
 int esc_render_strips(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
                       int32_t strip_rows, int32_t first_strip, int32_t strip_stride,
                       const esc_render_options *opts, float *d_rgb_f32, uint8_t *d_rgb_u8);
@@ -408,7 +414,10 @@ int esc_strip_local_rows(int32_t H, int32_t strip_rows, int32_t first_strip,
  * only valid while the context's per-camera / per-scene device state stands: esc_frame_launch
  * returns ESC_ERR_INVALID once the context has rendered another camera, size or scene, or had a
  * scene uploaded, or has freed or reallocated any buffer a frame kernel reads or writes (record
- * again).  Counters accumulate as for plain frames.  ESC_RENDER_TIME_KERNELS cannot be recorded. */
+ * again).  Counters accumulate as for plain frames.  ESC_RENDER_TIME_KERNELS cannot be recorded.
+ * Outputs and alignment as for esc_render_strips, checked before anything is launched or captured: a
+ * misaligned d_rgb_f32 is ESC_ERR_INVALID, *out is not written, and frames recorded earlier stay valid.
+ * Every esc_frame_launch writes the same elements again and nothing else. */
 typedef struct esc_frame esc_frame;
 int esc_frame_record(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t strip_rows,
                      int32_t first_strip, int32_t strip_stride, const esc_render_options *opts,
@@ -421,7 +430,11 @@ void esc_frame_destroy(esc_frame *frame);
 
 /* After a gather of N such buffers to one device (block r at d_gathered + r*rank_pitch_bytes):
  * writes the H x W frame in (h*W+w) order.  bytes_per_pixel = 12 (fp32 RGB) or 3 (u8 RGB).
- * Asynchronous on the context's stream. */
+ * Exactly H * W * bytes_per_pixel bytes of d_frame are written; of a rank's block only its local rows
+ * are read, so padding behind them (rank_pitch_bytes larger than the block) never reaches the frame;
+ * d_gathered is not modified and must not overlap d_frame.  With a pixel size that is a multiple of 4
+ * bytes both device pointers must be 4-byte aligned (ESC_ERR_INVALID, nothing launched); byte pixels
+ * may sit at any address.  Asynchronous on the context's stream. */
 int esc_assemble_strips(esc_context *ctx, const void *d_gathered, int32_t n_ranks,
                         size_t rank_pitch_bytes, int32_t W, int32_t H, int32_t strip_rows,
                         int32_t bytes_per_pixel, void *d_frame);
