@@ -14,10 +14,10 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math -fno-slp-vectorize \
             -Iinclude -I$(PKG)/host -I$(PKG)/csrc -Wall -Wno-unused-function
 
-LIB_SRC  := $(PKG)/csrc/rt_kernels.hip $(PKG)/csrc/rt_query.hip $(PKG)/csrc/rt_shade_rays.hip $(PKG)/csrc/rt_trace.hip $(PKG)/csrc/rt_adaptive.hip $(PKG)/csrc/rt_ambient.hip $(PKG)/csrc/rt_environ.hip $(PKG)/csrc/rt_gbuffer.hip $(PKG)/csrc/rt_filter.hip $(PKG)/csrc/rt_temporal.hip $(PKG)/csrc/rt_capi.cpp $(PKG)/csrc/rt_multi.cpp \
+LIB_SRC  := $(PKG)/csrc/rt_kernels.hip $(PKG)/csrc/rt_query.hip $(PKG)/csrc/rt_shade_rays.hip $(PKG)/csrc/rt_trace.hip $(PKG)/csrc/rt_adaptive.hip $(PKG)/csrc/rt_ambient.hip $(PKG)/csrc/rt_environ.hip $(PKG)/csrc/rt_gbuffer.hip $(PKG)/csrc/rt_filter.hip $(PKG)/csrc/rt_temporal.hip $(PKG)/csrc/rt_lens.hip $(PKG)/csrc/rt_capi.cpp $(PKG)/csrc/rt_multi.cpp \
             $(PKG)/host/host_core.cpp $(PKG)/host/obj_loader.cpp $(PKG)/host/synth.cpp \
             $(PKG)/host/accel_build.cpp $(PKG)/host/scene_tables.cpp
-LIB_HDR  := include/esctp1_rt.h $(PKG)/csrc/rt_device.h $(PKG)/csrc/rt_devmem.h $(PKG)/csrc/rt_math.h $(PKG)/csrc/rt_brute.h $(PKG)/csrc/rt_accel.h $(PKG)/csrc/rt_lists.h $(PKG)/csrc/rt_tile_math.h $(PKG)/csrc/rt_query.h $(PKG)/csrc/rt_query_sweep.h $(PKG)/csrc/rt_shade.h $(PKG)/csrc/rt_shade_rays.h $(PKG)/csrc/rt_shade_body.h $(PKG)/csrc/rt_shade_body.inc $(PKG)/csrc/rt_trace.h $(PKG)/csrc/rt_transmit.h $(PKG)/csrc/rt_adaptive.h $(PKG)/csrc/rt_ambient.h $(PKG)/csrc/rt_environ.h $(PKG)/csrc/rt_camera_ray.h $(PKG)/csrc/rt_gbuffer.h $(PKG)/csrc/rt_filter.h $(PKG)/csrc/rt_temporal.h $(PKG)/host/scene.h $(PKG)/host/accel_build.h $(PKG)/host/scene_tables.h
+LIB_HDR  := include/esctp1_rt.h $(PKG)/csrc/rt_device.h $(PKG)/csrc/rt_devmem.h $(PKG)/csrc/rt_math.h $(PKG)/csrc/rt_brute.h $(PKG)/csrc/rt_accel.h $(PKG)/csrc/rt_lists.h $(PKG)/csrc/rt_tile_math.h $(PKG)/csrc/rt_query.h $(PKG)/csrc/rt_query_sweep.h $(PKG)/csrc/rt_shade.h $(PKG)/csrc/rt_shade_rays.h $(PKG)/csrc/rt_shade_body.h $(PKG)/csrc/rt_shade_body.inc $(PKG)/csrc/rt_trace.h $(PKG)/csrc/rt_transmit.h $(PKG)/csrc/rt_adaptive.h $(PKG)/csrc/rt_ambient.h $(PKG)/csrc/rt_environ.h $(PKG)/csrc/rt_camera_ray.h $(PKG)/csrc/rt_gbuffer.h $(PKG)/csrc/rt_filter.h $(PKG)/csrc/rt_temporal.h $(PKG)/csrc/rt_lens.h $(PKG)/host/scene.h $(PKG)/host/accel_build.h $(PKG)/host/scene_tables.h
 
 all: lib viewer oracle
 

@@ -18,7 +18,7 @@ from ._capi import (ESC_FACE_FIXED, ESC_FACE_HASH, ESC_STAGE_AUTO, ESC_STAGE_BVH
                     ESC_STAGE_SMEM, ESC_TRANSMIT_OFF, ESC_TRANSMIT_REFRACT, ESC_TRANSMIT_FRESNEL, EscError,
                     check)
 
-__all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "TemporalAccumulator", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "live_device_allocations", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table", "environment_sky", "environment_lookup_host",
+__all__ = ["Scene", "Camera", "Renderer", "RecordedFrame", "TemporalAccumulator", "FlatScene", "MultiRenderer", "render_multi", "render_multi_rccl", "rccl_available", "strip_local_rows", "live_device_allocations", "trace", "write_ppm", "quantise", "synthetic_view", "ambient_table", "lens_table", "environment_sky", "environment_lookup_host",
            "EscError", "ESC_FACE_FIXED", "ESC_FACE_HASH", "ESC_STAGE_AUTO", "ESC_STAGE_SMEM",
            "ESC_STAGE_LDS", "ESC_STAGE_BVH", "ESC_RENDER_EXACT_ONLY", "ESC_RENDER_TIME_KERNELS", "ESC_RENDER_INDEX_ORDER", "ESC_RENDER_SHADE_QUEUE",
            "ESC_RENDER_SHADE_FUSED", "ESC_RENDER_NO_TILE_LISTS", "ESC_RENDER_NO_LIGHT_LISTS", "ESC_RENDER_TWO_KERNELS", "ESC_RENDER_BVH_HEURISTIC_PADS", "ESC_RENDER_NO_COUNTERS", "ESC_RENDER_NO_PACKED_LIGHT_LISTS", "ESC_RENDER_VOTE", "ESC_TRANSMIT_OFF", "ESC_TRANSMIT_REFRACT", "ESC_TRANSMIT_FRESNEL", "version"]
@@ -273,6 +273,16 @@ def ambient_table(sets, samples, seed=0):
     or any other array of local directions of that shape."""
     out = np.zeros((int(sets), int(samples), 3), np.float32) if sets > 0 and samples > 0 else np.zeros(3, np.float32)
     check(_capi.load().esc_ambient_cosine_table(int(sets), int(samples), int(seed) & (2 ** 64 - 1), _fp(out)))
+    return out
+
+
+def lens_table(sets, samples, seed=0):
+    """esc_lens_disk_table: (sets, samples, 2) float32 points of the unit disk, made on the host (no GPU
+    needed) and deterministic in (sets, samples, seed): jittered over a grid when samples is a square, mapped
+    concentrically onto the disk, shuffled inside each set.  Renderer.set_lens_table takes it, or any other
+    array of lens points of that shape."""
+    out = np.zeros((int(sets), int(samples), 2), np.float32) if sets > 0 and samples > 0 else np.zeros(2, np.float32)
+    check(_capi.load().esc_lens_disk_table(int(sets), int(samples), int(seed) & (2 ** 64 - 1), _fp(out)))
     return out
 
 
@@ -1155,6 +1165,66 @@ class Renderer:
             to = _capi.esc_trace_options(int(max_depth), float(bias), mode, 0)
             check(self._lib.esc_render_traced_ex(self._h, C.byref(camera.c), W, H, int(spp), C.byref(o),
                                                  C.byref(to), *out))
+        self.synchronize()
+        return (img.cpu().numpy(), u8.cpu().numpy()) if want_u8 else img.cpu().numpy()
+
+    # ---- thin-lens camera (esc_set_lens_table / esc_lens_rays / esc_render_lens) -------------------------
+    def set_lens_table(self, table):
+        """esc_set_lens_table: table is a (sets, samples, 2) float32 array of points of the unit disk
+        (lens_table makes one), 1 <= sets, samples <= 64, or None to remove the table.  It belongs to the
+        renderer and survives uploads.  Its contents are not validated.  Synchronises."""
+        if table is None:
+            check(self._lib.esc_set_lens_table(self._h, 0, 0, None))
+            return
+        t = np.ascontiguousarray(table, dtype=np.float32)
+        if t.ndim != 3 or t.shape[2] != 2:
+            raise ValueError("table must have shape (sets, samples, 2)")
+        check(self._lib.esc_set_lens_table(self._h, t.shape[0], t.shape[1], _fp(t)))
+
+    @property
+    def lens_table_shape(self):
+        """(sets, samples) of the renderer's lens table, (0, 0) when none is set"""
+        s, k = C.c_int32(-1), C.c_int32(-1)
+        check(self._lib.esc_get_lens_table_shape(self._h, C.byref(s), C.byref(k)))
+        return int(s.value), int(k.value)
+
+    def lens_rays(self, camera, W, H, *, aperture, focus_dist, sample=0, seed=0, rows=None, offsets=None):
+        """The frame's primary rays through a thin lens (esc_lens_rays) as device tensors (origins, dirs),
+        laid out as camera_rays' and with its rows and offsets: a ray starts at lens point `sample` of its
+        pixel's set of the lens table, scaled by `aperture` (the lens radius), and aims at the point of the
+        plane at `focus_dist` along the view axis that the pinhole ray meets.  seed picks the sets.
+        aperture=0 gives camera_rays' bits and needs no table.  Asynchronous."""
+        import torch
+        r0, r1 = (0, H) if rows is None else (int(rows[0]), int(rows[1]))
+        n = max(0, (r1 - r0) * W)
+        dev = torch.device("cuda", self.device)
+        o = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        d = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        po = None if offsets is None else self._query_ptr("offsets", offsets, torch.float32, (n, 2))
+        lo = _capi.esc_lens_options(float(aperture), float(focus_dist), int(seed) & (2 ** 64 - 1))
+        check(self._lib.esc_lens_rays(self._h, C.byref(camera.c), W, H, r0, r1, po, C.byref(lo), int(sample),
+                                      C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr())))
+        return o, d
+
+    def render_lens(self, camera, W, H, *, spp, aperture, focus_dist, lens_seed=0, max_depth=0, bias=1e-4,
+                    transmission="off", want_u8=False, shadows=True, face_mode=ESC_FACE_FIXED, fixed_face=0,
+                    seed=0, exact=False):
+        """Frame with depth of field (esc_render_lens): render_traced with sample k of every pixel sent
+        through lens point k of the pixel's set (lens_rays), so spp <= the table's samples per set.  The
+        plane at focus_dist stays sharp.  aperture=0 is render_traced, bit for bit.  Returns numpy fp32
+        (H, W, 3) and optionally the quantised bytes.  Synchronous; trace_stats / transmit_stats report it."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        img = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        u8 = torch.empty((H, W, 3), dtype=torch.uint8, device=dev) if want_u8 else None
+        o = _options(shadows, face_mode, fixed_face, seed, ESC_STAGE_AUTO, 0,
+                     ESC_RENDER_EXACT_ONLY if exact else 0)
+        to = _capi.esc_trace_options(int(max_depth), float(bias), _transmit_mode(transmission), 0)
+        lo = _capi.esc_lens_options(float(aperture), float(focus_dist), int(lens_seed) & (2 ** 64 - 1))
+        torch.cuda.current_stream(dev).synchronize()  # the buffers were made on torch's stream
+        check(self._lib.esc_render_lens(self._h, C.byref(camera.c), W, H, int(spp), C.byref(o), C.byref(to),
+                                        C.byref(lo), C.c_void_p(img.data_ptr()),
+                                        None if u8 is None else C.c_void_p(u8.data_ptr())))
         self.synchronize()
         return (img.cpu().numpy(), u8.cpu().numpy()) if want_u8 else img.cpu().numpy()
 

@@ -125,6 +125,11 @@ class esc_transmit_stats(C.Structure):  # 24 bytes
     _fields_ = [("refracted", C.c_uint64), ("fresnel_reflected", C.c_uint64), ("total_internal", C.c_uint64)]
 
 
+class esc_lens_options(C.Structure):  # 24 bytes
+    _fields_ = [("aperture", C.c_float), ("focus_dist", C.c_float), ("seed", C.c_uint64),
+                ("reserved", C.c_int32 * 2)]
+
+
 class esc_adaptive_options(C.Structure):  # 16 bytes
     _fields_ = [("spp", C.c_int32), ("threshold", C.c_float), ("band_rows", C.c_int32), ("reserved", C.c_int32)]
 
@@ -324,6 +329,14 @@ SIGNATURES = {
     "esc_environment_sky": (C.c_int, [C.c_int32, _F, _F, _F, _F]),
     "esc_environment_rays": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
     "esc_environment_lookup_host": (C.c_int, [C.c_int32, _F, C.c_int64, _F, _F]),
+    "esc_set_lens_table": (C.c_int, [_P, C.c_int32, C.c_int32, _F]),
+    "esc_get_lens_table_shape": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "esc_lens_disk_table": (C.c_int, [C.c_int32, C.c_int32, C.c_uint64, _F]),
+    "esc_lens_rays": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                C.POINTER(esc_lens_options), C.c_int32, _P, _P]),
+    "esc_render_lens": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32, C.c_int32,
+                                  C.POINTER(esc_render_options), C.POINTER(esc_trace_options),
+                                  C.POINTER(esc_lens_options), _P, _P]),
     "esc_render_frame_host": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,
                                         C.POINTER(esc_render_options), _F, _U8]),
     "esc_render_frame_multi": (C.c_int, [_P, C.POINTER(esc_camera), C.c_int32, C.c_int32,

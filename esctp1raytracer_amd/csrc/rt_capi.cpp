@@ -24,6 +24,7 @@
 #include "rt_devmem.h"
 #include "rt_filter.h"
 #include "rt_gbuffer.h"
+#include "rt_lens.h"
 #include "rt_query.h"
 #include "rt_shade_rays.h"
 #include "rt_temporal.h"
@@ -70,6 +71,7 @@ extern "C" int esc_launch_adaptive_refine(const esc::AdaptiveRefineParams *p, hi
 extern "C" int esc_launch_ambient(const esc::AmbientParams *p, int camera, int sky, hipStream_t stream);
 extern "C" int esc_launch_add_light(const esc::AddLightParams *p, hipStream_t stream);
 extern "C" int esc_launch_environment_rays(const esc::EnvRaysParams *p, hipStream_t stream);
+extern "C" int esc_launch_lens_rays(const esc::LensRayParams *p, hipStream_t stream);
 extern "C" int esc_launch_modulate(const esc::ModulateParams *p, hipStream_t stream);
 extern "C" int esc_launch_gbuffer(const esc::GBufferParams *p, int camera, hipStream_t stream);
 extern "C" int esc_launch_filter_pack(const esc::FilterPackParams *p, hipStream_t stream);
@@ -246,6 +248,10 @@ struct esc_context {
   // context's, not the scene's.  nullptr: traced rays that miss stay black
   esc::EnvTexel *d_env = nullptr;
   int32_t env_res = 0;
+  // the lens table of esc_set_lens_table (rt_lens.h): lens_sets x lens_samples x 2 floats, points of the unit
+  // disk; the context's, not the scene's.  nullptr: only aperture 0 renders
+  float *d_lens = nullptr;
+  int32_t lens_sets = 0, lens_samples = 0;
   // the G-buffer (rt_gbuffer.hip): esc_gbuffer_stats' device counters, allocated by the first call
   unsigned long long *d_gbstats = nullptr;
   // esc_filter_guided (rt_filter.hip): esc_filter_stats' device counters and the last call's W*H, and the
@@ -2558,9 +2564,22 @@ int esc_last_trace_stats(esc_context *ctx, esc_trace_stats *out) {
   return ESC_OK;
 }
 
+// A ray maker of the traced frame: writes the n rays of sample k of pixels [p0, p0 + n) with the sub-pixel
+// offset (dx, dy).  arg: the maker's own (pinhole_rays: unused; lens_frame_rays: the esc_lens_options)
+typedef int (*RayMaker)(esc_context *ctx, const char *fn, const esc_camera *cam, int32_t W, int32_t H,
+                        const void *arg, int k, int64_t p0, int64_t n, float dx, float dy, float *d_o, float *d_d);
+
+// the pinhole rays of a band's sample: esc_render_supersampled's (k is the lens sample, which a pinhole has not)
+static int pinhole_rays(esc_context *ctx, const char *fn, const esc_camera *cam, int32_t W, int32_t H, const void *,
+                        int, int64_t p0, int64_t n, float dx, float dy, float *d_o, float *d_d) {
+  return camera_launch(ctx, fn, cam, W, H, p0, n, nullptr, dx, dy, d_o, d_d);
+}
+
+// The traced frame's loop over bands x samples: make_rays -> trace_launch -> k_ss_accumulate -> k_ss_finish
 static int render_traced_impl(const char *fn, esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
                               int32_t spp, int32_t max_depth, float bias, int32_t transmission,
-                              const esc_render_options *opts, float *d_image, uint8_t *d_u8) {
+                              const esc_render_options *opts, float *d_image, uint8_t *d_u8,
+                              RayMaker make_rays, const void *maker_arg) {
   int nn = 0;
   int rc = frame_args_ok(ctx, fn, cam, W, H, spp, opts, d_image, nn);
   if (rc) return rc;
@@ -2583,7 +2602,7 @@ static int render_traced_impl(const char *fn, esc_context *ctx, const esc_camera
       // esc_render_supersampled's sample k
       const float dx = ((float)(k % nn) + 0.5f) / (float)nn - 0.5f;
       const float dy = ((float)(k / nn) + 0.5f) / (float)nn - 0.5f;
-      if ((rc = camera_launch(ctx, fn, cam, W, H, p0, n, nullptr, dx, dy, d_o, d_d))) return rc;
+      if ((rc = make_rays(ctx, fn, cam, W, H, maker_arg, k, p0, n, dx, dy, d_o, d_d))) return rc;
       if ((rc = trace_launch(ctx, fn, n, d_o, d_d, (uint32_t)p0, opts, opts->seed + (uint64_t)k, max_depth, bias,
                              transmission, d_rgb, nullptr, d_queues)))
         return rc;
@@ -2606,7 +2625,7 @@ int esc_render_traced(esc_context *ctx, const esc_camera *cam, int32_t W, int32_
                       int32_t max_depth, float bias, const esc_render_options *opts, float *d_image,
                       uint8_t *d_u8) {
   return render_traced_impl("esc_render_traced", ctx, cam, W, H, spp, max_depth, bias, ESC_TRANSMIT_OFF, opts,
-                            d_image, d_u8);
+                            d_image, d_u8, pinhole_rays, nullptr);
 }
 
 int esc_render_traced_ex(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
@@ -2620,7 +2639,235 @@ int esc_render_traced_ex(esc_context *ctx, const esc_camera *cam, int32_t W, int
   const int rc = transmit_args_ok(fn, topts);
   if (rc) return rc;
   return render_traced_impl(fn, ctx, cam, W, H, spp, topts->max_depth, topts->bias, topts->transmission, opts,
-                            d_image, d_u8);
+                            d_image, d_u8, pinhole_rays, nullptr);
+}
+
+// ---- thin-lens camera (rt_lens.h, rt_lens.hip) -----------------------------------------------------
+int esc_lens_disk_table(int32_t sets, int32_t samples, uint64_t seed, float *out) {
+  const char *fn = "esc_lens_disk_table";
+  if (sets < 1 || sets > esc::kLensMaxDim || samples < 1 || samples > esc::kLensMaxDim) {
+    set_error(std::string(fn) + ": sets and samples must be in 1..64");
+    return ESC_ERR_INVALID;
+  }
+  if (!out) {
+    set_error(std::string(fn) + ": out is null");
+    return ESC_ERR_INVALID;
+  }
+  // splitmix64 from (seed, sets, samples), tagged so that the stream is not the ambient table's
+  uint64_t st = seed ^ ((uint64_t)sets << 48) ^ ((uint64_t)samples << 40) ^ 0x4C454E53ull;
+  auto next = [&st]() {
+    uint64_t z = (st += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return ((double)(z >> 11) + 0.5) * 0x1p-53;
+  };
+  int grid = 0; // n when samples == n*n: one jittered point per cell
+  for (int n = 1; n <= 8; ++n)
+    if (n * n == samples) grid = n;
+  const double quarter_pi = 0.78539816339744830961566084581988, half_pi = 1.5707963267948966192313216916398;
+  for (int32_t s = 0; s < sets; ++s) {
+    float *row = out + 2 * (size_t)s * samples;
+    for (int32_t c = 0; c < samples; ++c) {
+      const double u1 = next(), u2 = next();
+      const double x = grid ? ((double)(c % grid) + u1) / (double)grid : ((double)c + u1) / (double)samples;
+      const double y = grid ? ((double)(c / grid) + u2) / (double)grid : u2;
+      // the concentric map of the square [-1, 1]^2 onto the unit disk
+      const double a = 2.0 * x - 1.0, b = 2.0 * y - 1.0;
+      double r = 0.0, phi = 0.0;
+      if (a != 0.0 || b != 0.0) {
+        if (std::fabs(a) > std::fabs(b)) {
+          r = a;
+          phi = quarter_pi * (b / a);
+        } else {
+          r = b;
+          phi = half_pi - quarter_pi * (a / b);
+        }
+      }
+      float fx = (float)(r * std::cos(phi)), fy = (float)(r * std::sin(phi));
+      while ((double)fx * fx + (double)fy * fy > 1.0) { // the casts may have rounded a rim point outwards
+        fx *= 1.f - 0x1p-24f;
+        fy *= 1.f - 0x1p-24f;
+      }
+      row[2 * c] = fx;
+      row[2 * c + 1] = fy;
+    }
+    for (int32_t m = samples - 1; m >= 1; --m) { // Fisher-Yates: lens sample k is not sub-pixel cell k
+      int32_t j = (int32_t)(next() * (double)(m + 1));
+      if (j > m) j = m;
+      std::swap(row[2 * m], row[2 * j]);
+      std::swap(row[2 * m + 1], row[2 * j + 1]);
+    }
+  }
+  return ESC_OK;
+}
+
+int esc_set_lens_table(esc_context *ctx, int32_t sets, int32_t samples, const float *host_table) {
+  const char *fn = "esc_set_lens_table";
+  if (!ctx) {
+    set_error(std::string(fn) + ": ctx is null");
+    return ESC_ERR_INVALID;
+  }
+  if ((sets == 0) != (host_table == nullptr)) {
+    set_error(std::string(fn) + ": sets == 0 goes with host_table == NULL (no table), and only with it");
+    return ESC_ERR_INVALID;
+  }
+  if (sets != 0 && (sets < 1 || sets > esc::kLensMaxDim || samples < 1 || samples > esc::kLensMaxDim)) {
+    set_error(std::string(fn) + ": sets and samples must be in 1..64");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream)); // a call in flight may still read the old table
+  ctx->lens_sets = ctx->lens_samples = 0;
+  const size_t floats = sets ? (size_t)sets * samples * 2 : 0;
+  const int rc = ctx->call.alloc(ctx->d_lens, floats); // sets == 0: freed, stays null
+  if (rc || sets == 0) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->d_lens, host_table, floats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream)); // host_table is the caller's again
+  ctx->lens_sets = sets;
+  ctx->lens_samples = samples;
+  return ESC_OK;
+}
+
+int esc_get_lens_table_shape(esc_context *ctx, int32_t *sets, int32_t *samples) {
+  if (!ctx || !sets || !samples) {
+    set_error(!ctx ? "esc_get_lens_table_shape: ctx is null" : "esc_get_lens_table_shape: sets or samples is null");
+    return ESC_ERR_INVALID;
+  }
+  *sets = ctx->lens_sets;
+  *samples = ctx->lens_samples;
+  return ESC_OK;
+}
+
+// the lens checks esc_lens_rays and esc_render_lens share, after ctx and lens are known not to be null.
+// last: the highest lens sample the call reads (`what` names the argument it comes from)
+static int lens_options_ok(const esc_context *ctx, const char *fn_, const esc_lens_options *lens, int32_t last,
+                           const char *what) {
+  const std::string fn(fn_);
+  if (!(lens->aperture >= 0.f) || !std::isfinite(lens->aperture)) {
+    set_error(fn + ": aperture must be finite and >= 0");
+    return ESC_ERR_INVALID;
+  }
+  if (!(lens->focus_dist > 0.f) || !std::isfinite(lens->focus_dist)) {
+    set_error(fn + ": focus_dist must be finite and > 0");
+    return ESC_ERR_INVALID;
+  }
+  if (lens->reserved[0] != 0 || lens->reserved[1] != 0) {
+    set_error(fn + ": reserved must be 0");
+    return ESC_ERR_INVALID;
+  }
+  if (last < 0) {
+    set_error(fn + ": " + what + " is negative");
+    return ESC_ERR_INVALID;
+  }
+  if (lens->aperture == 0.f) return ESC_OK; // a pinhole reads no table
+  if (!ctx->d_lens) {
+    set_error(fn + ": no lens table (esc_set_lens_table) while aperture > 0");
+    return ESC_ERR_INVALID;
+  }
+  if (last >= ctx->lens_samples) {
+    set_error(fn + ": " + what + " is beyond the lens table's samples per set");
+    return ESC_ERR_INVALID;
+  }
+  return ESC_OK;
+}
+
+// k_lens_rays on n rays of an already validated call
+static int lens_launch(esc_context *ctx, const char *fn, const esc_camera *cam, int32_t W, int32_t H, int64_t pix0,
+                       int64_t n, const float *d_offsets, float dx, float dy, const esc_lens_options *lens,
+                       int32_t sample, float *d_origins, float *d_dirs) {
+  if (n == 0) return ESC_OK;
+  esc::LensRayParams p;
+  std::memset(&p, 0, sizeof(p));
+  std::memcpy(p.origin, cam->origin, 12);
+  std::memcpy(p.llc, cam->lower_left_corner, 12);
+  std::memcpy(p.horizontal, cam->horizontal, 12);
+  std::memcpy(p.vertical, cam->vertical, 12);
+  esc::lens_axis(cam->horizontal, p.U);
+  esc::lens_axis(cam->vertical, p.V);
+  p.aperture = lens->aperture;
+  p.focus_dist = lens->focus_dist;
+  p.W = W;
+  p.H = H;
+  p.pix0 = pix0;
+  p.n = n;
+  p.offsets = d_offsets;
+  p.dx = dx;
+  p.dy = dy;
+  p.table = ctx->d_lens;
+  p.sets = ctx->lens_sets;
+  p.samples = ctx->lens_samples;
+  p.sample = sample;
+  p.seed = lens->seed;
+  p.orig = d_origins;
+  p.dir = d_dirs;
+  const int e = esc_launch_lens_rays(&p, ctx->stream);
+  if (e) {
+    set_error(std::string(fn) + ": k_lens_rays launch: " + hipGetErrorString((hipError_t)e));
+    return ESC_ERR_HIP;
+  }
+  return ESC_OK;
+}
+
+int esc_lens_rays(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t row_begin,
+                  int32_t row_end, const float *d_offsets, const esc_lens_options *lens, int32_t sample,
+                  float *d_origins, float *d_dirs) {
+  const char *fn = "esc_lens_rays";
+  if (!ctx || !cam || !lens) {
+    set_error(!ctx ? "esc_lens_rays: ctx is null" : !cam ? "esc_lens_rays: cam is null"
+                                                         : "esc_lens_rays: lens options are null");
+    return ESC_ERR_INVALID;
+  }
+  if (W < 2 || H < 2 || row_begin < 0 || row_end > H || row_begin > row_end) {
+    set_error("esc_lens_rays: need W,H >= 2 and 0 <= row_begin <= row_end <= H");
+    return ESC_ERR_INVALID;
+  }
+  const int rc = lens_options_ok(ctx, fn, lens, sample, "sample");
+  if (rc) return rc;
+  const int64_t n = (int64_t)(row_end - row_begin) * W;
+  if (n > 0 && (!d_origins || !d_dirs)) {
+    set_error("esc_lens_rays: d_origins and d_dirs are required");
+    return ESC_ERR_INVALID;
+  }
+  if (((uintptr_t)d_offsets | (uintptr_t)d_origins | (uintptr_t)d_dirs) & 3u) {
+    set_error("esc_lens_rays: device pointers must be 4-byte aligned");
+    return ESC_ERR_INVALID;
+  }
+  if (n > (int64_t)0xffffffffu * 256) {
+    set_error("esc_lens_rays: too many rays for one launch");
+    return ESC_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  return lens_launch(ctx, fn, cam, W, H, (int64_t)row_begin * W, n, d_offsets, 0.f, 0.f, lens, sample, d_origins,
+                     d_dirs);
+}
+
+// the lens rays of a band's sample: lens sample k (a RayMaker; arg: the call's esc_lens_options)
+static int lens_frame_rays(esc_context *ctx, const char *fn, const esc_camera *cam, int32_t W, int32_t H,
+                           const void *arg, int k, int64_t p0, int64_t n, float dx, float dy, float *d_o,
+                           float *d_d) {
+  return lens_launch(ctx, fn, cam, W, H, p0, n, nullptr, dx, dy, static_cast<const esc_lens_options *>(arg), k, d_o,
+                     d_d);
+}
+
+int esc_render_lens(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
+                    const esc_render_options *opts, const esc_trace_options *topts, const esc_lens_options *lens,
+                    float *d_image, uint8_t *d_u8) {
+  const char *fn = "esc_render_lens";
+  if (!ctx || !topts || !lens) {
+    set_error(!ctx ? "esc_render_lens: ctx is null"
+                   : !topts ? "esc_render_lens: trace options are null" : "esc_render_lens: lens options are null");
+    return ESC_ERR_INVALID;
+  }
+  int rc = transmit_args_ok(fn, topts);
+  if (rc) return rc;
+  if (spp < 1) {
+    set_error(std::string(fn) + ": spp must be n*n with n in 1..8");
+    return ESC_ERR_INVALID;
+  }
+  if ((rc = lens_options_ok(ctx, fn, lens, spp - 1, "spp"))) return rc;
+  return render_traced_impl(fn, ctx, cam, W, H, spp, topts->max_depth, topts->bias, topts->transmission, opts,
+                            d_image, d_u8, lens_frame_rays, lens);
 }
 
 // ---- environment cube map (rt_environ.h, rt_environ.hip) -------------------------------------------

@@ -73,6 +73,13 @@
 //                 by the visibility, the image gains, pixel by pixel, kd times the mean of what the open ones
 //                 of the K directions see of the sky (esc_render_skylight, esc_add_light; one GPU, not with
 //                 --ispc)
+//   --aperture A  with --spp N: depth of field.  Sample k of a pixel leaves lens point k of one of 16 sets of N
+//                 points of a disk of radius A (finite, >= 0; scene units) about the eye and aims at the plane
+//                 that stays sharp (esc_lens_disk_table, esc_set_lens_table, esc_render_lens).  Combines with
+//                 --bounces, --refract, --fresnel and --sky; not with --adaptive, --ao, --ispc or --gpus
+//   --focus D     with --aperture: the distance of the sharp plane along the view axis (finite, > 0; default
+//                 the fp32 length of look-at minus view)
+//   --lens-seed S with --aperture: seed of the lens table and of the per-pixel draw of a set (default 0)
 //   --help        print the options and leave
 #include <chrono>
 #include <cmath>
@@ -134,6 +141,8 @@ const char *kUsage =
     "  --sky-res N                with --sky: texels per side of the environment cube (1..1024, default 64)\n"
     "  --skylight                 with --sky and --ao K --ao-radius R: add the sky's light on the open directions\n"
     "                             to the image instead of multiplying it by the visibility\n"
+    "  --aperture A               with --spp: depth of field through a lens of radius A (scene units)\n"
+    "  --focus D --lens-seed S    with --aperture: the sharp plane's distance (|look - eye|), the lens seed (0)\n"
     "  --help                     this text\n";
 
 // --ao's values: a whole number in [lo, hi], or a finite float (> 0, or >= 0), with nothing after it
@@ -212,6 +221,9 @@ int main(int argc, char *argv[]) {
   bool have_temporal_extra = false, have_ao_seed = false;
   float sky_colours[9] = {0};
   int sky_res = 64;
+  float aperture = 0.f, focus = 0.f;
+  unsigned long long lens_seed = 0;
+  bool have_aperture = false, have_focus = false, have_lens_seed = false;
 
   for (int arg = 1; arg < argc; arg++) {
     const std::string a = argv[arg];
@@ -365,6 +377,27 @@ int main(int argc, char *argv[]) {
       continue;
     }
     if (a == "--skylight") { skylight = true; continue; }
+    if (a == "--aperture") {
+      aperture = parse_finite("--aperture", next, true);
+      have_aperture = true;
+      arg++;
+      continue;
+    }
+    if (a == "--focus") {
+      focus = parse_finite("--focus", next, false);
+      have_focus = true;
+      arg++;
+      continue;
+    }
+    if (a == "--lens-seed") {
+      if (!next) die("--lens-seed needs S");
+      char *end = nullptr;
+      lens_seed = std::strtoull(next, &end, 0);
+      if (end == next || *end != '\0') die(std::string("--lens-seed must be a whole number, got ") + next);
+      have_lens_seed = true;
+      arg++;
+      continue;
+    }
     if (a == "--help") {
       std::cout << kUsage;
       return 0;
@@ -397,6 +430,9 @@ int main(int argc, char *argv[]) {
   if (have_sky_res && !sky) die("--sky-res needs --sky");
   if (sky && (ispc || flat || gpus != 1)) die("--sky renders on one GPU and not with --ispc, --bvh or --bvh-tree");
   if (sky && have_adaptive) die("--sky is seen by traced frames: not with --adaptive");
+  if (have_aperture && !spp) die("--aperture needs --spp");
+  if (have_aperture && (have_adaptive || ao)) die("--aperture renders traced frames: not with --adaptive or --ao");
+  if (!have_aperture && (have_focus || have_lens_seed)) die("--focus and --lens-seed need --aperture");
 
   esc_scene *scene = esc_scene_new();
   if (!scene) die("out of memory");
@@ -492,6 +528,24 @@ int main(int argc, char *argv[]) {
       std::vector<float> cube((size_t)6 * sky_res * sky_res * 3);
       check(esc_environment_sky(sky_res, sky_colours, sky_colours + 3, sky_colours + 6, cube.data()), "sky");
       check(esc_set_environment(ctx, sky_res, cube.data()), "sky");
+    }
+    if (have_aperture) {
+      // 16 sets of spp lens points, one set per pixel; sample k of a pixel goes through lens point k
+      const int lens_sets = 16;
+      std::vector<float> table((size_t)lens_sets * spp * 2);
+      check(esc_lens_disk_table(lens_sets, spp, lens_seed, table.data()), "lens table");
+      check(esc_set_lens_table(ctx, lens_sets, spp, table.data()), "lens table");
+      if (!have_focus) { // the look-at point stays sharp
+        const float v[3] = {look[0] - eye[0], look[1] - eye[1], look[2] - eye[2]};
+        focus = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+        if (!(focus > 0.f) || !std::isfinite(focus)) die("--aperture: the view and the look-at point coincide; give --focus");
+      }
+      const esc_trace_options to = {bounces >= 0 ? bounces : 0, bias,
+                                    refract ? ESC_TRANSMIT_REFRACT : fresnel ? ESC_TRANSMIT_FRESNEL : ESC_TRANSMIT_OFF,
+                                    0};
+      const esc_lens_options lo = {aperture, focus, lens_seed, {0, 0}};
+      check(esc_render_lens(ctx, &cam, W, H, spp, &so, &to, &lo, d_image, nullptr), "render");
+    } else if (sky) {
       const esc_trace_options to = {bounces >= 0 ? bounces : 0, bias,
                                     refract ? ESC_TRANSMIT_REFRACT : fresnel ? ESC_TRANSMIT_FRESNEL : ESC_TRANSMIT_OFF,
                                     0};

@@ -1291,6 +1291,89 @@ int esc_environment_rays(esc_context *ctx, int64_t n, const float *d_dirs, float
  * compiled for the host.  texels in the host layout above, dirs and rgb n*3 floats in host memory. */
 int esc_environment_lookup_host(int32_t res, const float *texels, int64_t n, const float *dirs, float *rgb);
 
+/* ---- thin-lens camera: depth of field for camera rays and traced frames (rt_lens.h, rt_lens.hip,
+ * DESIGN.md section 3.22) ----
+ * An extension beyond the reference, whose camera.h:31-34 sends every ray of a pixel through one point.  Here
+ * a ray starts at a point of a lens disk of radius `aperture` about the camera's origin and aims at the point
+ * where the pinhole ray meets the plane at distance `focus_dist` along the view axis: that plane stays sharp,
+ * everything nearer or farther blurs.  The points of the disk are DATA the caller supplies (the lens table),
+ * like the ambient table; the device runs no transcendental and the rule is comparable bit for bit.
+ *
+ * The lens table: S sets x K samples x 2 floats, 1 <= S, K <= 64, points (x, y) of the unit disk, row-major:
+ * table[set][k] at 2*(set*K + k).  Its contents are never validated.
+ *
+ * All arithmetic is fp32, one rounding per written operation, no contraction; normalize, vector +- and
+ * vector x scalar in vec.h's operation order; only + - * / and sqrt.  The ray of pixel (w, h) with sub-pixel
+ * offset (dx, dy), lens sample index k and pixel id q = h*W + w:
+ *
+ *   is = (float(w) + dx) / float(W-1);   it = (float(h) + dy) / float(H-1)
+ *   p  = ((llc + horizontal*is) + vertical*it) - origin
+ *   if aperture == 0:   o' = origin;  d' = normalize(p)                      (esc_camera_rays' statements)
+ *   else:
+ *       U   = normalize(horizontal);   V = normalize(vertical)
+ *       set = mix(lens.seed, q, 0xFFFFFFFD) mod S
+ *             (the mixer of esc_trace_options, high 32 bits; 0xFFFFFFFE and 0xFFFFFFFF are taken by the
+ *             ambient set and the Fresnel draw, and no light has this index)
+ *       l   = table[set][k]
+ *       off = U*(l.x*aperture) + V*(l.y*aperture)
+ *       o'  = origin + off
+ *       d'  = normalize(p*focus_dist - off)
+ *
+ * camera.h:16-29 puts the image plane at distance 1, so p has axial component 1 and origin + p*focus_dist
+ * lies on the focus plane; the line of (o', d') passes it whatever l is.  `set` does not depend on k: the spp
+ * samples of a pixel walk one set and so stay stratified over the lens.  A degenerate camera makes NaN rays,
+ * as written.  With aperture == 0 nothing new is computed and the table is not read.  A lens ray is an
+ * ordinary ray to the sweeps: it passes the precondition gate or runs the reference loop, as any
+ * caller-supplied ray does. */
+typedef struct esc_lens_options { /* 24 bytes */
+  float aperture;      /* the lens radius in scene units: finite, >= 0 */
+  float focus_dist;    /* distance along the view axis of the plane that stays sharp: finite, > 0 */
+  uint64_t seed;       /* picks each pixel's set of the table */
+  int32_t reserved[2]; /* must be 0 */
+} esc_lens_options;
+/* host_table: sets*samples*2 floats in HOST memory, copied to the device.  The table belongs to the context
+ * and survives scene uploads; a new one replaces it; sets == 0 with host_table == NULL removes it (samples is
+ * then ignored).  Synchronises the context's stream before and after.  sets or samples outside 1..64, or
+ * exactly one of sets == 0 / host_table == NULL, is ESC_ERR_INVALID. */
+int esc_set_lens_table(esc_context *ctx, int32_t sets, int32_t samples, const float *host_table);
+/* *sets, *samples = the shape of the context's lens table, 0 and 0 when none is set */
+int esc_get_lens_table_shape(esc_context *ctx, int32_t *sets, int32_t *samples);
+/* A table of uniformly distributed lens points, on the host, without a context or a device, deterministic in
+ * its three arguments.  out: sets*samples*2 floats.  Random numbers: splitmix64 from
+ * seed ^ (sets << 48) ^ (samples << 40) ^ 0x4C454E53, u = ((x >> 11) + 0.5) * 2^-53 in (0, 1).  Per set: when
+ * samples is a square n*n, cell c = j*n + i of an n x n grid gets the point ((i + u1)/n, (j + u2)/n) of the
+ * unit square, otherwise point c is ((c + u1)/samples, u2); the point (a, b) = (2x - 1, 2y - 1) goes through the
+ * concentric square-to-disk map (|a| > |b|: r = a, phi = (pi/4)*(b/a); else r = b, phi = pi/2 - (pi/4)*(a/b);
+ * (0, 0) stays) to (r cos phi, r sin phi); then the set's points are shuffled (Fisher-Yates, j = floor(u*(m+1))
+ * for m = samples-1 .. 1), so that lens sample k is not tied to sub-pixel cell k.  All in double with the
+ * host's libm, then cast to float and, if the cast left x*x + y*y above 1, scaled by 1 - 2^-24 until it is
+ * not.  The result is data a caller can read, store or replace.  sets or samples outside 1..64 or a null
+ * pointer is ESC_ERR_INVALID. */
+int esc_lens_disk_table(int32_t sets, int32_t samples, uint64_t seed, float *out);
+/* The frame's primary rays through the lens, as data: esc_camera_rays' twin with the same layout, alignment,
+ * n == 0 and asynchrony rules.  Ray i = (h - row_begin)*W + w of rows [row_begin, row_end) is the ray above
+ * with (dx, dy) = d_offsets[2i], d_offsets[2i+1] (NULL: 0), lens sample `sample` and q = h*W + w.  Needs a
+ * table and 0 <= sample < K unless lens.aperture == 0, where the rays are esc_camera_rays', bit for bit.
+ * ESC_ERR_INVALID, with nothing launched: an aperture that is negative, NaN or infinite, a focus_dist that is
+ * not finite or not > 0, a non-zero reserved word, a sample beyond the table, no table while aperture > 0, a
+ * NULL or misaligned pointer, and esc_camera_rays' argument errors.  No scene is needed. */
+int esc_lens_rays(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t row_begin,
+                  int32_t row_end, const float *d_offsets, const esc_lens_options *lens, int32_t sample,
+                  float *d_origins, float *d_dirs);
+/* Frame with depth of field: esc_render_traced_ex with every sample's ray sent through the lens.  Sample k of
+ * spp = n*n takes the grid offset of esc_render_supersampled, lens sample k, pixel id h*W + w and seed
+ * opts.seed + k, and is traced as esc_trace_rays_ex traces it; the same sum in sample order, the same
+ * division by float(spp) and quantisation, the same bands with at most 256 MB of scratch, and
+ * esc_last_trace_stats / esc_last_transmit_stats report it.  Needs K >= spp unless lens.aperture == 0.  With
+ * aperture == 0 the frame is esc_render_traced_ex's, bit for bit (and with max_depth == 0 and no environment
+ * esc_render_supersampled's).  The environment rule above applies unchanged.  ESC_ERR_INVALID, with nothing
+ * launched: the lens errors of esc_lens_rays (spp in place of sample) and esc_render_traced_ex's argument
+ * errors.  Out of scope: a lens in the frame kernels or in the adaptive, ambient, sky-light and G-buffer
+ * frames, polygonal apertures, bokeh weights, chromatic aberration, motion blur. */
+int esc_render_lens(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H, int32_t spp,
+                    const esc_render_options *opts, const esc_trace_options *trace_opts,
+                    const esc_lens_options *lens, float *d_image, uint8_t *d_u8);
+
 /* Whole frame into HOST memory, synchronous: render + D2H.  `image` = W*H*3 floats. */
 int esc_render_frame_host(esc_context *ctx, const esc_camera *cam, int32_t W, int32_t H,
                           const esc_render_options *opts, float *image, uint8_t *rgb8);
